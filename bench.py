@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — self-play games/sec at fixed MCTS sims (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K timed steps (the figures
+taken inside those steps by events - roofline, roofline_net, roofline_tree, time_share - come with them), the JSON line.
+`--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy (dump_outputs below; inputs and
+seeds depend on the arguments only, so two builds can be compared array for array).  `--full` adds everything that
+takes runs of its own: the `value_*` legs beside the headline and `cpu_baseline`.
 
 N > 1 needs one rank per GPU (RCCL).  Either the caller starts the ranks (`python -m
 torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: WORLD_SIZE is set, bench.py is a
@@ -22,7 +28,7 @@ positions, per-game seeds base+g.  Games shard across GPUs with no data-path col
 The headline runs with the result-identical root evaluation carry-over (the new root's priors are the ones the
 played child received during the previous ply's search: 6 network forwards per ply instead of the reference's 7,
 games bit-identical, tests/test_gpu_round3.py) and evaluator row compaction (slots without a pending leaf are not
-network rows); `value_no_carry` (every root evaluated afresh, as the reference does) and
+network rows); with `--full`, `value_no_carry` (every root evaluated afresh, as the reference does) and
 `value_full_policy_head` (all 8,100 policy columns) are measured beside it on a few extra steps.
 
 Prints ONE JSON line (rank 0).  `roofline` = the dominant kernel of the step, the hand-written
@@ -31,7 +37,7 @@ launches (rows = games; the carried-over rounds launch it with zero rows and are
 the whole network forward over all launches and the rows they really evaluated; `roofline_tree` = the tree/rules
 kernel k_search_round (HBM-bound integer work); all measured live with events on the stream the kernels run on.
 `cpu_baseline` = the CPU oracle ("port" of the reference algorithm, net on CPU torch) timed on the
-host cores on a bounded sample (rank 0, N = 1 only).
+host cores on a bounded sample (rank 0, N = 1 only, `--full`).
 """
 import argparse
 import json
@@ -92,6 +98,61 @@ def pmc_traffic(kernel, G, S, blocks, fetch_factor=1.0):
                     name, ", " + doc["note"] if doc.get("note") else "",
                     "libxq_hip.so sha16 " + doc["build_libxq_hip_sha16"] if doc.get("build_libxq_hip_sha16") else "not recorded")
     return None, None
+
+
+DUMP_SAMPLE_GAMES = 256            # games whose records are written whole (board, move list, visit counts of every ply)
+DUMP_SCALAR_GAMES = 16384          # games whose per-ply scalars (z, player, n_moves, valid, chosen) are written
+DUMP_SEED = 20260
+
+
+def dump_outputs(path, records, n_games, outcomes=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step - the step's sample records
+    (`records`: uint8 tensor of n_games * 70 xq_sample_record, distributed.RECORD_DTYPE), decoded into float arrays and written
+    as path/<name>.npy.  All games' records would be 660 MB at the default size, so: the per-ply scalars of up to
+    DUMP_SCALAR_GAMES games (all of them at the default size) and the whole records of DUMP_SAMPLE_GAMES games, both chosen
+    by a fixed seed (the same games in every run with the same arguments); ~53 MB at the most.  Fields of plies that
+    hold no sample (valid = 0) and move-list entries past n_moves are written as 0 whatever the buffer holds there.
+    `outcomes`: this rank's per-game scalars (engine.read_game_outcomes), written as outcome_<key>.npy."""
+    import torch
+    from chinesechessai_amd import distributed as xd
+    os.makedirs(path, exist_ok=True)
+    P, RB = 70, xd.RECORD_BYTES
+    rec = records.view(n_games, P, RB)
+    rng = np.random.RandomState(DUMP_SEED)
+
+    def pick(k):
+        return np.arange(n_games) if n_games <= k else np.sort(rng.choice(n_games, size=k, replace=False))
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    # per-ply scalars: bytes 48..63 of every record
+    head_dtype = np.dtype([("z", "<f8"), ("player", "i1"), ("n_moves", "u1"), ("valid", "u1"), ("pad", "u1"),
+                           ("chosen", "<u2"), ("pad2", "<u2")])
+    gi = pick(DUMP_SCALAR_GAMES)
+    sel = rec if len(gi) == n_games else rec[torch.as_tensor(gi, device=rec.device)]
+    head = np.frombuffer(sel[:, :, 48:64].contiguous().cpu().numpy().tobytes(), dtype=head_dtype).reshape(len(gi), P)
+    valid = head["valid"] != 0
+    save("scalar_games", gi, np.float64)
+    save("valid", valid)
+    save("z", np.where(valid, head["z"], 0.0), np.float64)
+    for k in ("player", "n_moves", "chosen"):
+        save(k, np.where(valid, head[k], 0))
+    # whole records of the sampled games
+    si = pick(DUMP_SAMPLE_GAMES)
+    full = np.frombuffer(rec[torch.as_tensor(si, device=rec.device)].contiguous().cpu().numpy().tobytes(),
+                         dtype=xd.RECORD_DTYPE).reshape(len(si), P)
+    fv = full["valid"] != 0
+    s = np.arange(90)
+    code = ((full["board"][..., s // 8] >> (4 * (s % 8)).astype(np.uint32)) & 15).astype(np.int16)      # as distributed.unpack_board
+    board = np.where(code <= 7, code, 7 - code)
+    listed = fv[..., None] & (np.arange(128) < full["n_moves"][..., None])
+    save("sample_games", si, np.float64)
+    save("sample_board", np.where(fv[..., None], board, 0))
+    save("sample_moves", np.where(listed, full["moves"], 0))
+    save("sample_counts", np.where(listed, full["counts"], 0))
+    for k, v in (outcomes or {}).items():
+        save("outcome_" + k, v)
 
 
 # ------------------------------------------------------------------------------------------
@@ -184,9 +245,16 @@ def main():
     ap.add_argument("--games", type=int, default=16384, help="concurrent games per GPU")
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--blocks", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything that is reported beside the headline and takes runs of its own: the "
+                         "value_* legs (--aux-steps extra steps each) and cpu_baseline.  Off by default: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (its sample records, decoded; a fixed "
+                         "seeded sample of the games where all of them would be too much) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--warmup-plies", type=int, default=0, help="0 = full warmup steps; >0 shortens a warmup step to this many plies")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="cpu_baseline on whole 70-ply games (8 per worker, median of 3: ~100 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="with --full: cpu_baseline on whole 70-ply games (8 per worker, median of 3: ~100 s)")
     ap.add_argument("--refill", type=int, default=0, metavar="TOTAL",
                     help="steady-state mode (reported beside the headline, never instead of it): every step plays TOTAL games "
                          "per GPU through the --games concurrent slots, a finished game's slot being refilled with the next seed")
@@ -213,7 +281,7 @@ def main():
                          "evaluation carry-over is on (the played child's network evaluation becomes the next root's, 6 forwards "
                          "per ply); value_no_carry in the JSON line is this mode, measured beside the headline")
     ap.add_argument("--aux-steps", type=int, default=2,
-                    help="steps for each of the figures measured beside the headline at N = 1 (value_no_carry, "
+                    help="with --full: steps for each of the figures measured beside the headline at N = 1 (value_no_carry, "
                          "value_full_policy_head); 0 = skip them")
     ap.add_argument("--tree-reuse", action="store_true", help="extension: keep the played move's subtree (no reference oracle)")
     ap.add_argument("--virtual-loss", action="store_true", help="extension: up to 8 distinct leaves per game and round (8x the network rows)")
@@ -539,10 +607,16 @@ def run_rank(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
 
-    # ---- beside the headline (N = 1 only, a few steps each, outside the timed region): every root evaluated afresh
+    # ---- what the last timed step returned, before anything else plays into the same buffers
+    if args.dump_outputs:
+        last = pipe.drain() if use_dist else records                   # (N ranks: the gathered records of every rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, TG * world, outcomes)
+
+    # ---- beside the headline (--full, N = 1 only, a few steps each, outside the timed region): every root evaluated afresh
     # like the reference (no carry-over), and the full 8,100-column policy head
     aux = {}
-    if world == 1 and args.aux_steps > 0 and not args.profile_plies and not args.refill:
+    if args.full and world == 1 and args.aux_steps > 0 and not args.profile_plies and not args.refill:
         def timed_steps(ev_, base):
             torch.cuda.synchronize()
             ta = time.time()
@@ -761,7 +835,7 @@ def run_rank(args):
                       "draws_by_cap": int((outcomes["reason"] == 8).sum()), "errors": int(outcomes["error"].sum())},
         }
         out.update(aux)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.blocks, S, plies=70 if args.cpu_baseline_full else 18)
         print(json.dumps(out))
     eng.close()

@@ -1336,7 +1336,7 @@ def test_self_play_api_mirror_vs_reference_golden(L, golden_dir):
 
 def test_bench_contract_line(L, monkeypatch, capsys):
     """bench.py's one JSON line on a tiny workload, in process: every key of the driver's contract,
-    the two objects this tier adds (`roofline`, `cpu_baseline`), and the same again through the
+    the two objects this tier adds (`roofline`, and with `--full` `cpu_baseline`), and the same again through the
     RCCL code path with a single rank (init, all-gather of the sample records, barrier, MAX
     all-reduce of the time)."""
     import importlib
@@ -1355,7 +1355,7 @@ def test_bench_contract_line(L, monkeypatch, capsys):
         assert len(lines) == 1
         return json.loads(lines[0])
 
-    d = run(base)
+    d = run(base + ["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -1379,6 +1379,45 @@ def test_bench_contract_line(L, monkeypatch, capsys):
     import torch.distributed as dist
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(L, monkeypatch, capsys, tmp_path):
+    """A plain bench.py run carries none of the figures that take runs of their own (`value_*`, `cpu_baseline`: --full);
+    --steps sets the timed steps; --dump-outputs writes the last timed step's sample records as float32 / float64
+    arrays that are the same from run to run and agree with the games the engine reports."""
+    import importlib
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    bench = importlib.import_module("bench")
+    G = 300                                                    # more than bench.DUMP_SAMPLE_GAMES: the seeded sample is taken
+    assert G > bench.DUMP_SAMPLE_GAMES
+    dumps = []
+    for rep in range(2):
+        out = tmp_path / ("dump%d" % rep)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--games", str(G), "--sims", "16", "--blocks", "2", "--steps", "2",
+                                          "--warmup", "0", "--dump-outputs", str(out)])
+        bench.main()
+        lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and abs(d["value"] - G / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert "cpu_baseline" not in d and not [k for k in d if k.startswith("value_")] and "roofline" in d
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"z", "valid", "player", "n_moves", "chosen", "scalar_games", "sample_games", "sample_board",
+                                       "sample_moves", "sample_counts", "outcome_n_samples"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    assert a["z"].shape == (G, 70) and a["sample_counts"].shape == (bench.DUMP_SAMPLE_GAMES, 70, 128)
+    assert np.array_equal(a["scalar_games"], np.arange(G)) and np.array_equal(a["valid"].sum(axis=1), a["outcome_n_samples"])
+    si = a["sample_games"].astype(np.int64)
+    assert len(set(si.tolist())) == bench.DUMP_SAMPLE_GAMES and (np.diff(si) > 0).all() and si.max() < G
+    v = a["valid"][si] != 0
+    assert (a["sample_counts"].sum(axis=2)[v] == 16 - 8).all() and (a["sample_counts"][~v] == 0).all()   # S - 8 visits per ply (A10)
+    assert ((a["sample_moves"] != 0).sum(axis=2) <= a["n_moves"][si]).all() and (np.abs(a["sample_board"]) <= 7).all()
+    assert np.isfinite(a["z"]).all() and (a["z"][a["valid"] == 0] == 0).all()
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -3,8 +3,8 @@ set -e
 TAG=${1:-r03}
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > gpurun_out/${TAG}_bench_c3.json 2> gpurun_out/${TAG}_bench.err
 O=$GRAFT_REPO_ROOT/gpurun_out
+timeout -k 10 600 python bench.py --full > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench.err
 cd /tmp
 # (profiled passes evaluate every root and every leaf afresh: every launch of the network kernels is then a full-size one, so the per-kernel
 # averages and per-launch counter means are not diluted by the empty launches the carried-over roots leave behind)
