@@ -53,6 +53,9 @@ static_assert(sizeof(GameS) == 16, "GameS must be 16 bytes");
 static_assert(sizeof(xq_sample_record) == 576, "xq_sample_record layout is part of the ABI");
 
 enum : int { F_TERM = 2, F_VAL_NEG = 4, F_VAL_POS = 8, F_CHECK = 16 };
+// PATH_CAP: longest path of a search (levels below the root).  A fresh tree grows one level per round, so at most 64
+// (xq_engine_create); a kept subtree (tree reuse) keeps its depth, and the rules end a game at move_count >= 70, so a
+// path holds at most 70 - move_count moves.  Whatever walks a path serves one level per lane in strides of 64.
 enum : int { PATH_CAP = 72, LEAF_NONE = 0xFFFF };
 
 struct Eng {
@@ -331,13 +334,13 @@ __device__ int select_child(const Tree &T, int node)
 }
 
 // self_play.py:70-80: `mult` sequential updates of value v at the node on level `depth`
-// (levels: 0 = root, i = path_node[i-1]); every ancestor alternates the sign.
+// (levels: 0 = root, i = path_node[i-1]); every ancestor alternates the sign.  One lane per level, in strides of 64: a
+// path below a kept subtree (tree reuse) may be up to PATH_CAP levels deep; the levels of a path are distinct nodes.
 __device__ void backup(const Tree &T, int root, const uint16_t *path_node, int depth, double v, int mult)
 {
-    const int lane = XQ_LANE;
-    if (lane <= depth) {
-        const int x = lane == 0 ? root : path_node[lane - 1];
-        const double sv = ((depth - lane) & 1) ? -v : v;
+    for (int l = XQ_LANE; l <= depth; l += 64) {
+        const int x = l == 0 ? root : path_node[l - 1];
+        const double sv = ((depth - l) & 1) ? -v : v;
         double w = T.W[x];
         for (int i = 0; i < mult; i++) w += sv;
         T.W[x] = w;
@@ -461,12 +464,14 @@ __device__ void consume_eval(const Eng &E, int g, int slot, WaveLds &L, const Tr
         }
         if (lane == 0) { T.first[node] = (uint16_t)first; T.nc[node] = (uint8_t)n; E.n_nodes[g] = (uint32_t)(first + n); }
     }
-    if (lane < depth) L.path_node[lane] = E.leaf_path[(size_t)slot * PATH_CAP + lane];
+    for (int l = lane; l < depth; l += 64) L.path_node[l] = E.leaf_path[(size_t)slot * PATH_CAP + l];
     wave_sync();
     mem_fence_wave();
-    if (VL && lane <= depth) {                       // the pending visits of this leaf are real now
-        const int x = lane == 0 ? root : L.path_node[lane - 1];
-        T.vl[x] = (uint8_t)(T.vl[x] - mult);
+    if (VL) {                                        // the pending visits of this leaf are real now
+        for (int l = lane; l <= depth; l += 64) {
+            const int x = l == 0 ? root : L.path_node[l - 1];
+            T.vl[x] = (uint8_t)(T.vl[x] - mult);
+        }
     }
     backup(T, root, L.path_node, depth, v, mult);
     if (lane == 0) E.leaf_node[slot] = LEAF_NONE;
@@ -724,7 +729,7 @@ __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, 
 {
     const int lane = XQ_LANE;
     for (int j = lane; j < n; j += 64) E.leaf_moves[(size_t)slot * MAXM + j] = moves[j];
-    if (lane < depth) E.leaf_path[(size_t)slot * PATH_CAP + lane] = L.path_node[lane];
+    for (int l = lane; l < depth; l += 64) E.leaf_path[(size_t)slot * PATH_CAP + l] = L.path_node[l];
     const uint32_t my_dword = lane < 12 ? pack_dword(bd, lane) : 0u;
     if (!E.dedupe) {                                          // (with the dedupe: stored by dedupe_insert, past the L2)
         if (lane < 12) E.leaf_board[(size_t)slot * 12 + lane] = my_dword;
@@ -825,7 +830,7 @@ __device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int ba
             const int mine = (lane < nslot && E.leaf_node[(size_t)g * K + lane] == node) ? 1 : 0;
             const int k = __ffsll((unsigned long long)__ballot(mine)) - 1;
             if (lane == 0 && k >= 0) E.leaf_mult[(size_t)g * K + k] += 1;
-            if (lane <= depth) { const int x = lane == 0 ? root : L.path_node[lane - 1]; T.vl[x] += 1; }
+            for (int l = lane; l <= depth; l += 64) { const int x = l == 0 ? root : L.path_node[l - 1]; T.vl[x] += 1; }
             mem_fence_wave();
             sims_left--;
             continue;
@@ -878,7 +883,7 @@ __device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int ba
                 record_leaf(E, g * K + nslot, L, L.bd, st.side, node, depth, VL ? 1 : sims_left, L.legal, mr.n_legal,
                             planes, fmt);
                 if (!VL) return;
-                if (lane <= depth) { const int x = lane == 0 ? root : L.path_node[lane - 1]; T.vl[x] += 1; }
+                for (int l = lane; l <= depth; l += 64) { const int x = l == 0 ? root : L.path_node[l - 1]; T.vl[x] += 1; }
                 mem_fence_wave();
                 nslot++;
                 sims_left--;
@@ -1050,6 +1055,19 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
         uint32_t bN = 0;
         if (lane <= depth) { bW = T.W[bx]; bN = T.N[bx]; }
         if (lane < depth) L.path_node[lane] = (uint16_t)pth;
+        // levels 64 .. depth (a path below a kept subtree, tree reuse: up to PATH_CAP levels) in a second set of registers,
+        // lane l = level 64 + l; behind a wave-uniform branch: a path of at most 63 moves issues what it always did
+        const bool deep = depth >= 64;
+        int bx2 = 0;
+        double bW2 = 0.0;
+        uint32_t bN2 = 0;
+        if (deep) {
+            if (lane + 64 <= depth) {
+                bx2 = E.leaf_path[(size_t)slot * PATH_CAP + 63 + lane];
+                bW2 = T.W[bx2]; bN2 = T.N[bx2];
+            }
+            if (lane + 64 < depth) L.path_node[lane + 64] = E.leaf_path[(size_t)slot * PATH_CAP + 64 + lane];
+        }
         double v;
         float p0 = 0.f, p1 = 0.f;
         if (p_ec >= 0 && E.ec_on == 1) {
@@ -1121,6 +1139,11 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
         double w = bW;
         for (int i = 0; i < mult; i++) w += sv;
         if (lane <= depth) { T.W[bx] = w; T.N[bx] = bN + (uint32_t)mult; }
+        if (deep && lane + 64 <= depth) {                                    // (64 is even: level 64 + l carries lane l's sign)
+            double w2 = bW2;
+            for (int i = 0; i < mult; i++) w2 += sv;
+            T.W[bx2] = w2; T.N[bx2] = bN2 + (uint32_t)mult;
+        }
         if (lane == 0) E.leaf_node[slot] = LEAF_NONE;
         // ... and the same updates on the registers the descent reads
         r_N += (uint32_t)mult;
@@ -1254,6 +1277,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
                 }
                 for (int j = lane; j < mr.n_legal; j += 64) E.leaf_moves[(size_t)slot * MAXM + j] = L.legal[j];
                 if (lane < depth) E.leaf_path[(size_t)slot * PATH_CAP + lane] = L.path_node[lane];
+                if (depth > 64 && lane + 64 < depth) E.leaf_path[(size_t)slot * PATH_CAP + 64 + lane] = L.path_node[lane + 64];
                 if (STAMP && lane == 0) stp[8] = __builtin_amdgcn_s_memtime();
                 // (the packed board again from LDS: cheaper than a register held across the move generation)
                 const uint32_t bdw = lane < 12 ? pack_dword(L.bd, lane) : 0u;
@@ -2032,6 +2056,13 @@ struct xq_engine {
     bool row_map_fetched = false;             // xq_engine_row_map since row compaction was last switched: the evaluator knows the layout
     unsigned dd_tag = 0;                      // round tag of the leaf dedupe table (never 0: the cleared table's tag)
     unsigned ec_epoch = 16, ec_seq = 0;       // evaluation cache: ply counter (+2 at every new set of roots), launch counter
+    // The cache's key is the position (board + side), its payload the priors BY INDEX into the leaf's legal-move list - and
+    // that list also depends on the two king caches.  Play from roots whose caches say where the kings stand keeps them so
+    // (wave_make_move updates them on every king move and capture), so there the position fixes the list.  Roots handed to
+    // xq_engine_set_roots may carry any caches: if one of them disagrees with its board, the cache stays off (E.ec_on = 0,
+    // its statistics at 0) until the next xq_engine_new_games / set_roots / refill_begin with consistent roots.
+    int ec_want = 0;                          // what xq_engine_set_eval_cache asked for: 0 off, 1 on, 2 verify
+    bool ec_roots_ok = true;                  // the current games started from roots with true king caches
     // profiling
     int prof = 0;                             // 0 = off, N = HIP events around every N-th k_search_round (and every k_play_move)
     unsigned prof_seen = 0;
@@ -2040,6 +2071,19 @@ struct xq_engine {
     double search_ms = 0, play_ms = 0;
     int64_t search_n = 0, play_n = 0;
 };
+
+static void eval_cache_apply(xq_engine *e) { e->E.ec_on = e->ec_roots_ok ? e->ec_want : 0; }
+
+// both king caches of a caller's root name the square where that king stands (a missing king: NO_KING)
+static bool king_caches_true(const int8_t *board, int rk, int bk)
+{
+    int r = NO_KING, b = NO_KING, nr = 0, nb = 0;
+    for (int s = 0; s < 90; s++) {
+        if (board[s] == KING) { r = s; nr++; }
+        else if (board[s] == -KING) { b = s; nb++; }
+    }
+    return nr <= 1 && nb <= 1 && r == rk && b == bk;
+}
 
 template <class T> static int dalloc(xq_engine *e, T *&p, size_t count)
 {
@@ -2072,7 +2116,7 @@ extern "C" int xq_engine_create(const xq_config *cfg, xq_engine **out)
     if (!xq_device_ok(cfg->device)) return fail(XQ_E_NOGPU, "device is not gfx950: this library carries gfx950 code only");
     if (int rc = ensure_crc_table(cfg->device)) return rc;
     const int nrounds = (cfg->sims + cfg->leaf_batch - 1) / cfg->leaf_batch;
-    if (nrounds > 64) return fail(XQ_E_INVALID, "sims / leaf_batch too large (at most 64 rounds per move: one lane per path level)");
+    if (nrounds > 64) return fail(XQ_E_INVALID, "sims / leaf_batch too large (at most 64 rounds per move: a fresh tree's paths fit one lane per level)");
     const long ncap_l = 1 + (long)nrounds * MAXM;
     if (ncap_l > 65535) return fail(XQ_E_INVALID, "node arena exceeds 16-bit indices");
     xq_engine *e = new xq_engine();
@@ -2215,6 +2259,8 @@ extern "C" int xq_engine_new_games(xq_engine *e, const uint32_t *seeds)
     HIPCHK(hipStreamSynchronize(e->stream));          // u is a local: copy must finish
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));
     e->ec_epoch += 2;                                                    // new games, possibly new weights: nothing cached survives
+    e->ec_roots_ok = true;                                               // (the start position: true king caches)
+    eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
     hipLaunchKernelGGL(k_new_games, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());
@@ -2283,6 +2329,7 @@ extern "C" int xq_engine_set_tree_reuse(xq_engine *e, int enable)
     Eng &E = e->E;
     if (enable && E.eval_carry) return fail(XQ_E_INVALID, "tree reuse cannot be combined with root evaluation carry-over");
     E.tree_reuse = enable ? 1 : 0;
+    E.want_check = (enable || E.nrounds >= 12) ? 1 : 0;      // (a kept subtree's paths reach 12 plies with any number of rounds)
     if (int rc = grow_nodes(e)) return rc;
     HIPCHK(hipMemsetAsync(E.root_node, 0, (size_t)E.G * 2, e->stream));
     HIPCHK(hipMemsetAsync(E.n_nodes, 0, (size_t)E.G * 4, e->stream));
@@ -2383,6 +2430,10 @@ extern "C" int xq_engine_set_roots(xq_engine *e, const int8_t *boards, const int
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));     // k_set_roots counts them
     e->ec_epoch += 2;
+    e->ec_roots_ok = true;
+    for (size_t g = 0; g < G && e->ec_roots_ok; g++)
+        e->ec_roots_ok = king_caches_true(boards + g * 90, state[g * XQ_STATE_WORDS + XQ_S_RED_KING], state[g * XQ_STATE_WORDS + XQ_S_BLACK_KING]);
+    eval_cache_apply(e);
     e->active_posted = 0;
     hipLaunchKernelGGL(k_set_roots, dim3(e->E.G), dim3(64), 0, e->stream, e->E, e->stage_boards, e->stage_state);
     HIPCHK(hipGetLastError());
@@ -2538,7 +2589,7 @@ extern "C" int xq_engine_set_eval_cache(xq_engine *e, int log2_entries)
     if (!e) return fail(XQ_E_INVALID, "null engine");
     const bool verify = log2_entries < 0;          // (diagnostic: -log2_entries = the size; hits keep their rows and are compared)
     if (verify) log2_entries = -log2_entries;
-    if (log2_entries == 0) { e->E.ec_on = 0; return 0; }
+    if (log2_entries == 0) { e->ec_want = 0; eval_cache_apply(e); return 0; }
     if (log2_entries < 10 || log2_entries > 24) return fail(XQ_E_INVALID, "eval cache: 10 <= log2_entries <= 24");
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t n = (size_t)1 << log2_entries;
@@ -2553,7 +2604,8 @@ extern "C" int xq_engine_set_eval_cache(xq_engine *e, int log2_entries)
         e->E.ec_mask = (int)(n - 1);
     }
     e->ec_epoch += 2;
-    e->E.ec_on = verify ? 2 : 1;
+    e->ec_want = verify ? 2 : 1;
+    eval_cache_apply(e);                           // (off all the same while the games' roots carry stale king caches: xq_engine::ec_want)
     e->E.ec_stat_stride = e->E.G * 64;
     return 0;
 }
@@ -2727,6 +2779,8 @@ extern "C" int xq_engine_refill_begin(xq_engine *e, const uint32_t *seeds, int t
     HIPCHK(hipStreamSynchronize(e->stream));          // locals: the copies must finish
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));
     e->ec_epoch += 2;                                                    // new games, possibly new weights: nothing cached survives
+    e->ec_roots_ok = true;                                               // (the start position: true king caches)
+    eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
     hipLaunchKernelGGL(k_new_games, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());

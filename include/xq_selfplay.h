@@ -322,7 +322,11 @@ int  xq_engine_set_leaf_dedupe(xq_engine *e, int enable);
  * A negative log2_entries switches the cache to VERIFY mode with 2^-log2_entries entries: a leaf the cache could answer
  * is evaluated all the same and its priors, value and move count are compared with the entry's (a self-check of the
  * "depends on the position only" promise).  xq_engine_eval_cache_stats: leaves answered (verify mode: compared), entries
- * filled, and mismatches found in verify mode, since the last reset. */
+ * filled, and mismatches found in verify mode, since the last reset.
+ * The entry's priors are indexed by the leaf's legal-move list, which also depends on the two king caches: while any
+ * root handed to xq_engine_set_roots carries a king cache that does not name the square where that king stands
+ * (XQ_NO_KING for a missing king), the cache stays off and its statistics at 0; the next xq_engine_new_games /
+ * set_roots / refill_begin with consistent roots switches it on again. */
 int  xq_engine_set_eval_cache(xq_engine *e, int log2_entries);
 int  xq_engine_eval_cache_stats(xq_engine *e, uint64_t *hits_fills_mismatches_host /* [3] */, int reset);
 

@@ -1046,100 +1046,14 @@ def test_tree_reuse_is_opt_in_and_consistent(L):
 
 
 def _vl_search_mirror(S, leaf_batch=8):
-    """Test-side restatement (Python, NumPy float32 PUCT as the reference's select_child) of one
-    MCTS.search from the start position WITH virtual loss as the engine defines it: a pending visit
-    counts as N + 1, W - 1 on every node of its path; a round's pending leaves are expanded and
-    backed up in the order they were reached.  Rules and the evaluator: the oracle env / HashNet."""
-    import zlib
+    """One MCTS.search from the start position WITH virtual loss as the engine defines it (a pending visit counts as N + 1,
+    W - 1 on every node of its path; a round's pending leaves are expanded and backed up in the order they were reached),
+    restated in Python: tests/search_mirror.py.  Rules and the evaluator: the oracle env / HashNet."""
     from oracle import xq_oracle as xo
-
-    class Node:
-        __slots__ = ("N", "W", "P", "mv", "ch", "term", "val", "vl")
-
-        def __init__(self, P=np.float32(0), mv=0):
-            self.N, self.W, self.P, self.mv, self.ch, self.term, self.val, self.vl = 0, 0.0, P, mv, [], False, 0.0, 0
-
-    def hashnet(board, player, moves):
-        h0 = zlib.crc32(board.astype(np.int8).tobytes() + bytes([player & 0xff]))
-        pri = []
-        for mv in moves:
-            f, t = divmod(mv, 90)
-            h = zlib.crc32(bytes([f // 9, f % 9, t // 9, t % 9]), h0)
-            pri.append(np.float32(((h >> 8) % 64 + 1) / 1024))
-        return pri, ((h0 >> 4) % 65 - 32) / 64
-
-    def select(node):
-        sq = np.float32(np.sqrt(np.float64(node.N + node.vl)))
-        best, bi = None, -1
-        for i, c in enumerate(node.ch):
-            n, w = c.N + c.vl, c.W - float(c.vl)
-            q = np.float32(w / n) if n else np.float32(0)
-            t = np.float32(1.5) * c.P
-            t = t * sq
-            t = t / np.float32(1 + n)
-            sc = q + t
-            if best is None or sc > best:
-                best, bi = sc, i
-        return node.ch[bi]
-
-    def backup(root, path, v, mult):
-        depth = len(path)
-        for lvl in range(depth + 1):
-            x = root if lvl == 0 else path[lvl - 1]
-            sv = -v if ((depth - lvl) & 1) else v
-            for _ in range(mult):
-                x.W += sv
-            x.N += mult
-
-    root = Node()
-    pending = []
-
-    def consume():
-        for node, path, mult, moves, pri, val in pending:
-            node.ch = [Node(p, m) for p, m in zip(pri, moves)]
-            for x in [root] + path:
-                x.vl -= mult
-            backup(root, path, val, mult)
-        pending.clear()
-
-    done = 0
-    while done < S:
-        batch = min(leaf_batch, S - done)
-        consume()
-        for _ in range(batch):
-            node, path = root, []
-            while node.ch:
-                node = select(node)
-                path.append(node)
-            if not node.term and node.vl:
-                for e in pending:
-                    if e[0] is node:
-                        e[2] += 1
-                for x in [root] + path:
-                    x.vl += 1
-                continue
-            if not node.term:
-                env = xo.OracleEnv()
-                env.reset()
-                for x in path:
-                    env.make_move(x.mv)
-                legal = env.legal_moves()
-                w = int(env.e.winner)
-                if legal and w == xo.WINNER_NONE:
-                    side = int(env.e.current_player)
-                    pri, val = hashnet(env.board().reshape(90), side, legal)
-                    pending.append([node, list(path), 1, legal, pri, val])
-                    for x in [root] + path:
-                        x.vl += 1
-                    continue
-                node.term = True
-                side = int(env.e.current_player)
-                node.val = 1.0 if w == side else (-1.0 if w == -side else 0.0)
-            backup(root, path, node.val, 1)
-        done += batch
-    consume()
-    assert root.vl == 0
-    return [c.mv for c in root.ch], [c.N for c in root.ch], root
+    from tests.search_mirror import Node, hashnet_evaluate, search_mirror
+    env = xo.OracleEnv()
+    env.reset()
+    return search_mirror(env, Node(), S, leaf_batch, virtual_loss=True, evaluate=hashnet_evaluate)
 
 
 def test_virtual_loss_is_opt_in_and_matches_its_restatement(L):
