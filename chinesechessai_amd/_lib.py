@@ -182,6 +182,14 @@ _SIGNATURES = {
     "xq_engine_refill_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "xq_engine_refill_read_games": (C.c_int, [C.c_void_p] * 8),
     "xq_engine_refill_read_slots": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "xq_engine_set_pairing": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "xq_engine_refill_begin2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "xq_engine_search_round2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "xq_engine_end_search2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "xq_engine_row_map_net": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "xq_engine_read_row_history_net": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "xq_engine_eval_hashnet2": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "xq_conv3x3_nhwc_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int]),
     "xq_heads_nhwc_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int]),

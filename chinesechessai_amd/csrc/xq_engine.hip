@@ -127,7 +127,22 @@ struct Eng {
     // nVl counts the pending visits through a node and is folded into PUCT as N + vl, W - vl
     int vloss, leaf_slots;
     uint8_t *nVl;
+    // ---- per-slot network selection (xq_engine_search_round2): pairing[g] = 0 network 0 moves both sides of the game in slot
+    // g, 1 = network 0 is red and network 1 black; a ply's whole tree is searched with the network of the side to move at
+    // the root.  two_net is set for the launches of a two-network round only: then a parked leaf carries its network in
+    // leaf_net[slot] (0 everywhere otherwise) and k_assign_rows numbers one row map per network.
+    uint8_t *pairing;         // [G]
+    uint8_t *leaf_net;        // [slots]
+    int two_net, n_slots;     // (n_slots: row_src of network 1 starts at row_src + n_slots)
+    // what fresh games get as their pairing (xq_engine_set_pairing, else the session default); the rows of each network in
+    // every round, [2][ROW_HIST]
+    const uint8_t *pairing_init;
+    int32_t *row_hist_net;
 };
+
+// the evaluator outputs a tree kernel consumes, one per network (single-network launches: twice the same)
+struct EvalOut { const void *a; const void *v; int kind; int pad; };
+struct EvalPair { EvalOut o[2]; };
 
 __device__ __forceinline__ void eval_cache_fill(const Eng &E, int i, uint32_t board_dword, int side, int n, float p0, float p1, float value);
 // (accessors of the evaluation cache: past the L2s - see eval_cache_fill)
@@ -389,12 +404,14 @@ __device__ void root_noise(const Eng &E, int g, int ply, int n, float &p0, float
 
 // self_play.py:61-68 + 146-148: expand the pending leaf with its priors and apply its backups
 template <bool VL>
-__device__ void consume_eval(const Eng &E, int g, int slot, WaveLds &L, const Tree &T, int root, int eval_kind,
-                             const void *ev_a, const void *ev_v, int ply)
+__device__ void consume_eval(const Eng &E, int g, int slot, WaveLds &L, const Tree &T, int root, const EvalPair &ev, int ply)
 {
     const int lane = XQ_LANE;
     const int node = E.leaf_node[slot];
     if (node == LEAF_NONE) return;
+    const int lnet = E.two_net ? (uni((int)E.leaf_net[slot]) != 0 ? 1 : 0) : 0;       // the leaf's network's outputs
+    const int eval_kind = ev.o[lnet].kind;
+    const void *const ev_a = ev.o[lnet].a, *const ev_v = ev.o[lnet].v;
     const int n = E.leaf_n[slot], mult = E.leaf_mult[slot], depth = E.leaf_depth[slot];
     const uint16_t *lm = E.leaf_moves + (size_t)slot * MAXM;
     double v;
@@ -528,6 +545,7 @@ __global__ __launch_bounds__(64) void k_new_games(Eng E)
 {
     __shared__ WaveLds L;
     new_game(E, blockIdx.x, L);
+    if (XQ_LANE == 0) E.pairing[blockIdx.x] = E.pairing_init[blockIdx.x];
 }
 
 // roots from caller-provided envs (one staged int8 board + int32 state row per game)
@@ -575,7 +593,7 @@ __global__ __launch_bounds__(64) void k_set_roots(Eng E, const int8_t *boards, c
 #endif
 // 64-bit hash of a position (12 packed board dwords, lane < 12, + side to move): wave-uniform.  Nothing trusts it: the
 // dedupe table and the evaluation cache compare boards in full.
-__device__ __forceinline__ uint64_t position_hash(uint32_t my_dword, int side)
+__device__ __forceinline__ uint64_t position_hash(uint32_t my_dword, int side, int net = 0)
 {
     const int lane = XQ_LANE;
     uint64_t h = 0;
@@ -586,7 +604,7 @@ __device__ __forceinline__ uint64_t position_hash(uint32_t my_dword, int side)
         h ^= ((uint64_t)hi << 32) | lo;
     }
     const uint32_t hlo = __builtin_amdgcn_readfirstlane((uint32_t)h), hhi = __builtin_amdgcn_readfirstlane((uint32_t)(h >> 32));
-    return mix64((((uint64_t)hhi << 32) | hlo) ^ (0x9E3779B97F4A7C15ull * (uint64_t)(side + 2)));
+    return mix64((((uint64_t)hhi << 32) | hlo) ^ (0x9E3779B97F4A7C15ull * (uint64_t)(side + 2 + 4 * net)));
 }
 
 // The evaluation cache is written and read by waves of every XCD: every access goes past the L2s (agent-scope atomics), like
@@ -618,7 +636,7 @@ struct DedupeLook {            // what dedupe_prepare hands to dedupe_finish
 // first half: publish the leaf's board and side (past the L2s), take a first look at the position's table entry.
 // Nothing of this wave enters the table here: the caller may do other work (move generation) while the stores land.
 __device__ __forceinline__ DedupeLook dedupe_prepare(const Eng &E, int slot, uint32_t my_dword /* lane < 12: packed board dword */, int side,
-                                                     uint64_t h)
+                                                     uint64_t h, int net = 0)
 {
     const int lane = XQ_LANE;
     // This leaf's board and side must be visible to every other wave before the table can hand them the slot.  The L2s of
@@ -627,6 +645,7 @@ __device__ __forceinline__ DedupeLook dedupe_prepare(const Eng &E, int slot, uin
     // agent-scope atomics (write-through / L2 bypass) and only their completion is waited for (dedupe_finish).
     if (lane < 12) __hip_atomic_store(&E.leaf_board[(size_t)slot * 12 + lane], my_dword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (lane == 0) __hip_atomic_store(&E.leaf_side[slot], (int8_t)side, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 1) __hip_atomic_store(&E.leaf_net[slot], (uint8_t)net, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     DedupeLook k;
     k.pos = (unsigned)h & (unsigned)E.dd_mask;
     // the first look at the table travels together with the stores above (the look is only a hint: the CAS decides)
@@ -677,7 +696,7 @@ __device__ __forceinline__ int eval_cache_probe(const Eng &E, uint64_t h, uint32
 }
 
 // second half: once the stores of dedupe_prepare have landed, enter the table
-__device__ __forceinline__ void dedupe_finish(const Eng &E, int slot, uint32_t my_dword, int side, DedupeLook k)
+__device__ __forceinline__ void dedupe_finish(const Eng &E, int slot, uint32_t my_dword, int side, DedupeLook k, int net = 0)
 {
     const int lane = XQ_LANE;
     const unsigned mask = (unsigned)E.dd_mask, tag = E.dd_tag;
@@ -699,7 +718,11 @@ __device__ __forceinline__ void dedupe_finish(const Eng &E, int slot, uint32_t m
         uint32_t theirs = 0;
         if (lane < 12) theirs = __hip_atomic_load(&E.leaf_board[(size_t)other * 12 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int oside = (int8_t)__hip_atomic_load(reinterpret_cast<const uint8_t *>(E.leaf_side) + other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool same = __ballot(lane < 12 && theirs != my_dword) == 0ull && oside == side;
+        // two networks: the same position waiting for the other network is another row (nothing trusts the hash, so the
+        // other slot's network is read like its side)
+        int onet = 0;
+        if (E.two_net) onet = (int)__hip_atomic_load(E.leaf_net + other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool same = __ballot(lane < 12 && theirs != my_dword) == 0ull && oside == side && onet == net;
         if (same) {
             if (lane == 0) {
                 // an entry only ever goes down: under a lower slot this one has lost already, no atomic needed (in the
@@ -718,14 +741,14 @@ __device__ __forceinline__ void dedupe_finish(const Eng &E, int slot, uint32_t m
     if (lane == 0) E.leaf_pos[slot] = (int32_t)pos;
 }
 
-__device__ __forceinline__ void dedupe_insert(const Eng &E, int slot, uint32_t my_dword /* lane < 12: packed board dword */, int side)
+__device__ __forceinline__ void dedupe_insert(const Eng &E, int slot, uint32_t my_dword /* lane < 12: packed board dword */, int side, int net = 0)
 {
-    dedupe_finish(E, slot, my_dword, side, dedupe_prepare(E, slot, my_dword, side, position_hash(my_dword, side)));
+    dedupe_finish(E, slot, my_dword, side, dedupe_prepare(E, slot, my_dword, side, position_hash(my_dword, side, net), net), net);
 }
 
 __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, const int8_t *bd, int side, int node,
                             int depth, int mult, const uint16_t *moves, int n, void *planes, int fmt,
-                            unsigned long long *st = nullptr)
+                            unsigned long long *st = nullptr, int net = 0)
 {
     const int lane = XQ_LANE;
     for (int j = lane; j < n; j += 64) E.leaf_moves[(size_t)slot * MAXM + j] = moves[j];
@@ -733,7 +756,7 @@ __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, 
     const uint32_t my_dword = lane < 12 ? pack_dword(bd, lane) : 0u;
     if (!E.dedupe) {                                          // (with the dedupe: stored by dedupe_insert, past the L2)
         if (lane < 12) E.leaf_board[(size_t)slot * 12 + lane] = my_dword;
-        if (lane == 0) E.leaf_side[slot] = (int8_t)side;
+        if (lane == 0) { E.leaf_side[slot] = (int8_t)side; E.leaf_net[slot] = (uint8_t)net; }
     }
     if (lane == 0) {
         E.leaf_node[slot] = (uint16_t)node; E.leaf_mult[slot] = (uint8_t)mult; E.leaf_n[slot] = (uint8_t)n;
@@ -741,16 +764,16 @@ __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, 
     }
     if (planes) write_planes(bd, side, planes, fmt, slot);
     if (st && lane == 0) st[8] = __builtin_amdgcn_s_memtime();
-    const uint64_t h = (E.dedupe || E.ec_on) ? position_hash(my_dword, side) : 0ull;
+    const uint64_t h = (E.dedupe || E.ec_on) ? position_hash(my_dword, side, net) : 0ull;
     DedupeLook look{ 0u, 0ull };
-    if (E.dedupe) look = dedupe_prepare(E, slot, my_dword, side, h);        // (board + side past the L2s, first look at the table)
+    if (E.dedupe) look = dedupe_prepare(E, slot, my_dword, side, h, net);   // (board + side past the L2s, first look at the table)
     int ec = -1;
     if (E.ec_on) {
         ec = eval_cache_probe(E, h, my_dword, side, 0ull, false, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
         if (lane == 0) E.leaf_ec[slot] = ec;
     }
     // (last: the planes' stores travel while it waits for the table; a leaf the cache answers needs no row at all)
-    if (E.dedupe && (ec < 0 || E.ec_on == 2)) dedupe_finish(E, slot, my_dword, side, look);
+    if (E.dedupe && (ec < 0 || E.ec_on == 2)) dedupe_finish(E, slot, my_dword, side, look, net);
     if (st && lane == 0) st[9] = __builtin_amdgcn_s_memtime();
 }
 
@@ -769,12 +792,14 @@ __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, 
 // wave).  Since round 5 only the virtual-loss build (K pending leaves per game, opt-in extension) runs this body; the
 // reference's search - one pending leaf per game and round - runs search_round_one below.
 template <bool VL>
-__device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int batch_count, int eval_kind,
-                                     const void *ev_a, const void *ev_v, void *planes, int fmt)
+__device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int batch_count, const EvalPair &ev,
+                                     void *planes, int fmt)
 {
     const int g = blockIdx.x, lane = XQ_LANE;
     const GameS gs = load_gs(E.gs + g);
     if (gs.done) return;
+    // the network that searches this ply = the network a parked leaf waits for: worked out where a leaf is parked
+    auto park_net = [&]() -> int { return (E.two_net && uni((int)E.pairing[g]) != 0 && gs.side != 1) ? 1 : 0; };
     const Tree T = tree_of(E, g);
     const int K = VL ? E.leaf_slots : 1;             // pending-leaf slots of this game: g * K + k
     int root = 0;
@@ -805,7 +830,7 @@ __device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int ba
     } else {
         root = E.root_node[g];
         for (int k = 0; k < K; k++)
-            consume_eval<VL>(E, g, g * K + k, L, T, root, eval_kind, ev_a, ev_v, gs.n_plies);
+            consume_eval<VL>(E, g, g * K + k, L, T, root, ev, gs.n_plies);
     }
 
     unpack_to_lds(E.board + (size_t)g * 12, L.root_bd);
@@ -839,7 +864,7 @@ __device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int ba
             if (node == root) {
                 // the root is never terminal (the driver checked legal moves, self_play.py:205-208)
                 record_leaf(E, g * K + nslot, L, L.root_bd, gs.side, root, 0, VL ? 1 : sims_left,
-                            E.root_moves + (size_t)g * MAXM, gs.n_root, planes, fmt);
+                            E.root_moves + (size_t)g * MAXM, gs.n_root, planes, fmt, nullptr, park_net());
                 if (!VL) return;
                 if (lane == 0) T.vl[root] += 1;
                 mem_fence_wave();
@@ -881,7 +906,7 @@ __device__ void search_round_generic(const Eng &E, WaveLds &L, int round, int ba
             if (!terminal) {
                 if (lane == 0) T.fl[node] = (uint8_t)flags;
                 record_leaf(E, g * K + nslot, L, L.bd, st.side, node, depth, VL ? 1 : sims_left, L.legal, mr.n_legal,
-                            planes, fmt);
+                            planes, fmt, nullptr, park_net());
                 if (!VL) return;
                 for (int l = lane; l <= depth; l += 64) { const int x = l == 0 ? root : L.path_node[l - 1]; T.vl[x] += 1; }
                 mem_fence_wave();
@@ -953,8 +978,8 @@ __device__ __forceinline__ int pick_child(int v0, int v1, int c)
 //   The leaf's packed board, its planes and the first look at the dedupe table leave right after the board is updated
 //   (wave_make_move's hook), so the table insert no longer waits a round trip behind ~3 KB of stores.
 template <bool STAMP>
-__device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_count, int eval_kind,
-                                 const void *ev_a, const void *ev_v, void *planes, int fmt, unsigned long long *stamps)
+__device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_count, const EvalPair &ev,
+                                 void *planes, int fmt, unsigned long long *stamps)
 {
     const int g = blockIdx.x, lane = XQ_LANE, slot = g;
     XQ_STAMP(0);
@@ -979,6 +1004,8 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     const int ec_v = *ec_p;
     const uint32_t lbw = lane < 12 ? E.leaf_board[(size_t)slot * 12 + lane] : 0u;      // (the pending leaf's position: key of the entry it fills)
     const int lside = E.leaf_side[slot];
+    int pair_v = 0;
+    if (E.two_net) pair_v = E.pairing[g];            // (two-network rounds only: a single-network round issues what it always did)
     int root = (round > 0 && E.tree_reuse) ? root_v : 0;
     int r_nc = T.nc[root], r_first = T.first[root];
     uint32_t r_N = T.N[root];
@@ -986,6 +1013,13 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     gx.u.x = (uint32_t)uni((int)gx.u.x); gx.u.y = (uint32_t)uni((int)gx.u.y);
     gx.u.z = (uint32_t)uni((int)gx.u.z); gx.u.w = (uint32_t)uni((int)gx.u.w);
     const GameS gs = gx.g;
+    // the network that searches this ply = the network of the side to move at the root: its outputs answer the pending
+    // leaf and the leaf this round parks waits for it (wave-uniform: scalar registers only)
+    const int cnet = (E.two_net && uni(pair_v) != 0 && gs.side != 1) ? 1 : 0;
+    // (both triples arrive with the other kernel arguments at the top; picking one is three scalar selects - indexing the
+    // argument by the network instead puts a scalar load between the first and the second memory round trip: +4 us)
+    const int eval_kind = cnet ? ev.o[1].kind : ev.o[0].kind;
+    const void *const ev_a = cnet ? ev.o[1].a : ev.o[0].a, *const ev_v = cnet ? ev.o[1].v : ev.o[0].v;
     const int ready = (round == 0 && E.eval_carry) ? ready_v : 0;
     int p_row = E.compact ? row_v : slot;
     if (round == 0) p_node = LEAF_NONE;
@@ -1195,6 +1229,13 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
         if (flags0 < 0) flags0 = T.fl[node0];
     }
 
+    // the network the parked leaf waits for = this ply's network again, worked out afresh where a leaf is parked (a
+    // two-network round loads its pairing byte a second time; held from the top it would cost every round a register)
+    auto park_net = [&]() -> int {
+        int pv = 0;
+        if (E.two_net) pv = E.pairing[g];
+        return (E.two_net && uni(pv) != 0 && gs.side != 1) ? 1 : 0;
+    };
     int sims_left = batch_count;
     bool first = true;
     while (sims_left > 0) {
@@ -1217,7 +1258,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
             if (node == root) {
                 // the root is never terminal (the driver checked legal moves, self_play.py:205-208)
                 record_leaf(E, slot, L, L.root_bd, gs.side, root, 0, sims_left, E.root_moves + (size_t)g * MAXM, gs.n_root,
-                            planes, fmt, stp);
+                            planes, fmt, stp, park_net());
                 return;
             }
             // ---- replay the path on a copy of the root env (_copy_env, self_play.py:156-175)
@@ -1249,18 +1290,20 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
             // the leaf's position is known the moment its last move is on the board: its packed board (for the dedupe:
             // past the L2s), its planes and the first look at its table entry leave before the move generation
             const int leaf_side = -st.side;
+            const int net = park_net();
             uint32_t my_dword = 0;
             uint64_t h = 0;
             unsigned long long ec_first = 0ull;
             DedupeLook look{ 0u, 0ull };
             auto early = [&](const int8_t *bd) {
                 my_dword = lane < 12 ? pack_dword(bd, lane) : 0u;
-                if (E.dedupe || E.ec_on) h = position_hash(my_dword, leaf_side);
+                if (E.dedupe || E.ec_on) h = position_hash(my_dword, leaf_side, net);
                 if (E.ec_on) ec_first = ec_ld64(&E.ec_state[eval_cache_pos(E, h)]);
-                if (E.dedupe) look = dedupe_prepare(E, slot, my_dword, leaf_side, h);
+                if (E.dedupe) look = dedupe_prepare(E, slot, my_dword, leaf_side, h, net);
                 else {
                     if (lane < 12) E.leaf_board[(size_t)slot * 12 + lane] = my_dword;
                     if (lane == 0) E.leaf_side[slot] = (int8_t)leaf_side;
+                    if (lane == 1) E.leaf_net[slot] = (uint8_t)net;
                 }
                 if (planes) write_planes(bd, leaf_side, planes, fmt, slot);
             };
@@ -1286,7 +1329,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
                     ec = eval_cache_probe(E, h, bdw, leaf_side, ec_first, true, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
                     if (lane == 0) E.leaf_ec[slot] = ec;
                 }
-                if (E.dedupe && (ec < 0 || E.ec_on == 2)) dedupe_finish(E, slot, bdw, leaf_side, look);
+                if (E.dedupe && (ec < 0 || E.ec_on == 2)) dedupe_finish(E, slot, bdw, leaf_side, look, net);
                 if (STAMP && lane == 0) stp[9] = __builtin_amdgcn_s_memtime();
                 return;
             }
@@ -1304,16 +1347,15 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
 
 // OCC = minimum waves per SIMD requested from the register allocator.
 template <int OCC, bool VL, bool STAMP = false>
-__global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int batch_count, int eval_kind,
-                                                          const void *ev_a, const void *ev_v, void *planes, int fmt,
+__global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int batch_count, EvalPair ev, void *planes, int fmt,
                                                           unsigned long long *stamps = nullptr)
 {
     // one wave = one game = one workgroup (packing 4 games into a 256-thread workgroup was
     // measured 20-40 % slower at the same register budget: a workgroup retires only with its
     // slowest game)
     __shared__ WaveLds L;
-    if constexpr (VL) search_round_generic<true>(E, L, round, batch_count, eval_kind, ev_a, ev_v, planes, fmt);
-    else search_round_one<STAMP>(E, L, round, batch_count, eval_kind, ev_a, ev_v, planes, fmt, stamps);
+    if constexpr (VL) search_round_generic<true>(E, L, round, batch_count, ev, planes, fmt);
+    else search_round_one<STAMP>(E, L, round, batch_count, ev, planes, fmt, stamps);
 }
 
 __constant__ uint32_t c_crc_table[256];
@@ -1324,13 +1366,14 @@ __device__ __forceinline__ uint32_t crc_byte(uint32_t crc, uint32_t b)
 }
 
 // exact dyadic evaluator: priors k/1024, values m/64 from CRC-32
-__global__ __launch_bounds__(64) void k_hashnet(Eng E, int salt)
+__global__ __launch_bounds__(64) void k_hashnet(Eng E, int salt0, int salt1)
 {
     __shared__ WaveLds L;
     const int g = blockIdx.x, lane = XQ_LANE;             // one block per pending-leaf slot
     if (E.gs[g / E.leaf_slots].done || E.leaf_node[g] == LEAF_NONE) return;
     unpack_to_lds(E.leaf_board + (size_t)g * 12, L.bd);
     wave_sync();
+    const int salt = E.leaf_net[g] ? salt1 : salt0;       // the salt of the network this leaf waits for
     uint32_t crc = 0xffffffffu;
     for (int s = 0; s < 90; s++) crc = crc_byte(crc, (uint32_t)(uint8_t)L.bd[s]);
     crc = crc_byte(crc, (uint32_t)(uint8_t)E.leaf_side[g]);
@@ -1351,6 +1394,11 @@ __global__ __launch_bounds__(64) void k_hashnet(Eng E, int salt)
 // network kernels touch only those rows.  One workgroup of 16 waves walks the G * K slots 1,024 at a time (ballot
 // prefix inside a wave, 16 partial sums through LDS).  row_src[row] = slot tells the trunk kernel where the search
 // kernel wrote that row's planes; leaf_row[slot] tells consume_eval where the row's logits and value are.
+// Two-network rounds (E.two_net): the same walk numbers one row map per network - the pending flags are split by
+// leaf_net, the two counts of a thread travel through the scan packed into one word (a pass holds at most 16,384 slots, so
+// each count fits 16 bits) - row_src of network 1 starts at row_src + n_slots, its count is row_count[1], and leaf_row[slot]
+// is the row inside the slot's own network's buffers.  Rows are in slot order within each network.  A single-network
+// round has every flag in network 0 and writes exactly what it always wrote.
 constexpr int ROW_HIST = 65536;
 
 __global__ __launch_bounds__(1024) void k_assign_rows(Eng E, int n_slots, unsigned seq)
@@ -1360,7 +1408,8 @@ __global__ __launch_bounds__(1024) void k_assign_rows(Eng E, int n_slots, unsign
     // that is over has none (its last leaves were consumed by k_end_search before k_play_move ended it).
     __shared__ int wtot[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int base = 0;
+    int base = 0, base1 = 0;
+    int32_t *const row_src1 = E.row_src + E.n_slots;
     for (int start = 0; start < n_slots; start += 16 * 1024) {
         const int s0 = start + tid * 16;
         uint32_t w[8] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu };
@@ -1414,22 +1463,39 @@ __global__ __launch_bounds__(1024) void k_assign_rows(Eng E, int n_slots, unsign
             dups &= flags;
             flags &= ~dups;
         }
-        const int mine = __popc(flags);
+        uint32_t net1 = 0;                                   // bit i: the leaf in slot s0 + i waits for network 1
+        if (E.two_net) {
+            if (s0 + 16 <= n_slots) {
+                const uint4 n4 = *reinterpret_cast<const uint4 *>(E.leaf_net + s0);
+                const uint32_t nw[4] = { n4.x, n4.y, n4.z, n4.w };
+#pragma unroll
+                for (int i = 0; i < 16; i++)
+                    if ((nw[i >> 2] >> ((i & 3) * 8)) & 0xffu) net1 |= 1u << i;
+            } else {
+                for (int i = 0; i < 16; i++)
+                    if (s0 + i < n_slots && E.leaf_net[s0 + i]) net1 |= 1u << i;
+            }
+            net1 &= flags;
+        }
+        const int mine = __popc(flags & ~net1) | (__popc(net1) << 16);     // rows of network 0 | rows of network 1 << 16
         int incl = mine;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
         if (lane == 63) wtot[wave] = incl;
         __syncthreads();
-        int off = base + incl - mine, total = 0;
+        int off = incl - mine, total = 0;
 #pragma unroll
         for (int k = 0; k < 16; k++) { const int c = wtot[k]; off += k < wave ? c : 0; total += c; }
         int rows[16];
-        int r = off;
+        int r = base + (off & 0xffff), r1 = base1 + (off >> 16);
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-            const bool p = (flags >> i) & 1u;
-            rows[i] = p ? r : -1;
-            if (p) { E.row_src[r] = s0 + i; r++; }
+            const bool p = (flags >> i) & 1u, n1 = (net1 >> i) & 1u;
+            rows[i] = p ? (n1 ? r1 : r) : -1;
+            if (p) {
+                if (n1) { row_src1[r1] = s0 + i; r1++; }
+                else { E.row_src[r] = s0 + i; r++; }
+            }
         }
         if (s0 + 16 <= n_slots) {
 #pragma unroll
@@ -1439,7 +1505,7 @@ __global__ __launch_bounds__(1024) void k_assign_rows(Eng E, int n_slots, unsign
             for (int i = 0; i < 16; i++)
                 if (s0 + i < n_slots) E.leaf_row[s0 + i] = rows[i];
         }
-        base += total;
+        base += total & 0xffff; base1 += total >> 16;
         __syncthreads();
         if (dups) {
             // the representative = the slot left in the group's table entry = the lowest slot of the group: its row was
@@ -1453,10 +1519,14 @@ __global__ __launch_bounds__(1024) void k_assign_rows(Eng E, int n_slots, unsign
                 }
         }
     }
-    if (tid == 0) { E.row_count[0] = base; E.row_hist[seq & (ROW_HIST - 1)] = base; }
+    if (tid == 0) {
+        E.row_count[0] = base; E.row_count[1] = base1;
+        E.row_hist[seq & (ROW_HIST - 1)] = base + base1;
+        E.row_hist_net[seq & (ROW_HIST - 1)] = base; E.row_hist_net[ROW_HIST + (seq & (ROW_HIST - 1))] = base1;
+    }
 }
 
-__global__ __launch_bounds__(64) void k_end_search(Eng E, int eval_kind, const void *ev_a, const void *ev_v)
+__global__ __launch_bounds__(64) void k_end_search(Eng E, EvalPair ev)
 {
     __shared__ WaveLds L;
     const int g = blockIdx.x;
@@ -1466,9 +1536,9 @@ __global__ __launch_bounds__(64) void k_end_search(Eng E, int eval_kind, const v
     const int root = E.root_node[g];
     if (E.vloss) {
         for (int k = 0; k < E.leaf_slots; k++)
-            consume_eval<true>(E, g, g * E.leaf_slots + k, L, T, root, eval_kind, ev_a, ev_v, gs.n_plies);
+            consume_eval<true>(E, g, g * E.leaf_slots + k, L, T, root, ev, gs.n_plies);
     } else {
-        consume_eval<false>(E, g, g, L, T, root, eval_kind, ev_a, ev_v, gs.n_plies);
+        consume_eval<false>(E, g, g, L, T, root, ev, gs.n_plies);
     }
 }
 
@@ -1509,7 +1579,7 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
     wave_sync();
 
     // sample record (self_play.py:234-239)
-    const bool store = (gs.side == 1) || !E.opponent_mode;
+    const bool store = (gs.side == 1) || E.pairing[g] == 0;          // the mover is network 0 (pairing 1: red plies only, self_play.py:234)
     if (store) {
         const size_t si = (size_t)g * XQ_MAX_PLIES + gs.n_samples;
         if (lane < 12) E.s_board[si * 12 + lane] = E.board[(size_t)g * 12 + lane];
@@ -1681,6 +1751,8 @@ struct Refill {
     GameS *out_gs;             // [total]
     xq_sample_record *records; // [total][70]
     int total;
+    const uint8_t *pair_all;   // [total] pairing by game id, NULL: pair_default for every game
+    int pair_default;
 };
 
 __global__ __launch_bounds__(64) void k_refill(Eng E, Refill R)
@@ -1703,7 +1775,10 @@ __global__ __launch_bounds__(64) void k_refill(Eng E, Refill R)
     for (int j = lane; j < XQ_MAX_PLIES; j += 64)
         E.uniforms[(size_t)g * XQ_MAX_PLIES + j] = R.uni_all[(size_t)nid * XQ_MAX_PLIES + j];
     new_game(E, g, L);
-    if (lane == 0) { R.slot_game[g] = nid; atomicAdd(R.active, 1); }
+    if (lane == 0) {
+        E.pairing[g] = R.pair_all ? R.pair_all[nid] : (uint8_t)R.pair_default;
+        R.slot_game[g] = nid; atomicAdd(R.active, 1);
+    }
 }
 
 // root children of every game (moves, visit counts, priors), zero-padded to 128
@@ -2052,6 +2127,9 @@ struct xq_engine {
     // refill mode (xq_engine_refill_*)
     double *uni_all = nullptr; int32_t *slot_game = nullptr, *next_game = nullptr; GameS *out_gs = nullptr;
     int refill_total = 0, refill_cap = 0;     // games of the running session / games the session buffers hold
+    uint8_t *pair_all = nullptr;              // [refill_cap] pairing by game id of the running refill session
+    bool refill_pairs = false;                // ... was handed in (else every game gets the session default)
+    uint8_t *pairing_init = nullptr;          // [G] what fresh games get (xq_engine_set_pairing, else cfg.opponent_mode everywhere)
     unsigned row_seq = 0;                     // search rounds launched with row compaction (index into row_hist)
     bool row_map_fetched = false;             // xq_engine_row_map since row compaction was last switched: the evaluator knows the layout
     unsigned dd_tag = 0;                      // round tag of the leaf dedupe table (never 0: the cleared table's tag)
@@ -2141,8 +2219,10 @@ extern "C" int xq_engine_create(const xq_config *cfg, xq_engine **out)
     bad |= dalloc(e, E.leaf_depth, G); bad |= dalloc(e, E.leaf_moves, G * MAXM); bad |= dalloc(e, E.leaf_path, G * PATH_CAP);
     bad |= dalloc(e, E.leaf_board, G * 12); bad |= dalloc(e, E.leaf_side, G);
     bad |= dalloc(e, E.priors, G * MAXM); bad |= dalloc(e, E.values, G);
-    bad |= dalloc(e, E.leaf_row, G); bad |= dalloc(e, E.row_src, G); bad |= dalloc(e, E.row_count, (size_t)1);
-    bad |= dalloc(e, E.row_hist, (size_t)ROW_HIST); bad |= alloc_dedupe(e, G);
+    bad |= dalloc(e, E.leaf_row, G); bad |= dalloc(e, E.row_src, 2 * G); bad |= dalloc(e, E.row_count, (size_t)2);
+    bad |= dalloc(e, E.row_hist, (size_t)ROW_HIST); bad |= dalloc(e, E.row_hist_net, (size_t)2 * ROW_HIST); bad |= alloc_dedupe(e, G);
+    bad |= dalloc(e, E.pairing, G); bad |= dalloc(e, e->pairing_init, G); bad |= dalloc(e, E.leaf_net, G + 16);
+    E.n_slots = E.G;
     bad |= dalloc(e, E.s_board, G * XQ_MAX_PLIES * 12); bad |= dalloc(e, E.s_player, G * XQ_MAX_PLIES);
     bad |= dalloc(e, E.s_n, G * XQ_MAX_PLIES); bad |= dalloc(e, E.s_moves, G * XQ_MAX_PLIES * MAXM);
     bad |= dalloc(e, E.s_counts, G * XQ_MAX_PLIES * MAXM); bad |= dalloc(e, E.s_z, G * XQ_MAX_PLIES);
@@ -2154,6 +2234,13 @@ extern "C" int xq_engine_create(const xq_config *cfg, xq_engine **out)
     if (bad) {
         xq_engine_destroy(e);
         return fail(XQ_E_HIP, "hipMalloc failed while sizing the engine");
+    }
+    E.pairing_init = e->pairing_init;
+    if (cfg->opponent_mode) {                   // opponent mode = "default pairing 1": network 0 red vs network 1 black
+        if (hipMemset(E.pairing, 1, G) != hipSuccess || hipMemset(e->pairing_init, 1, G) != hipSuccess) {
+            xq_engine_destroy(e);
+            return fail(XQ_E_HIP, "hipMemset failed while sizing the engine");
+        }
     }
     *out = e;
     return 0;
@@ -2359,9 +2446,10 @@ extern "C" int xq_engine_set_virtual_loss(xq_engine *e, int enable)
         bad |= dalloc(e, E.leaf_depth, S); bad |= dalloc(e, E.leaf_moves, S * MAXM); bad |= dalloc(e, E.leaf_path, S * PATH_CAP);
         bad |= dalloc(e, E.leaf_board, S * 12); bad |= dalloc(e, E.leaf_side, S);
         bad |= dalloc(e, E.priors, S * MAXM); bad |= dalloc(e, E.values, S);
-        bad |= dalloc(e, E.leaf_row, S); bad |= dalloc(e, E.row_src, S); bad |= alloc_dedupe(e, S);
+        bad |= dalloc(e, E.leaf_row, S); bad |= dalloc(e, E.row_src, 2 * S); bad |= alloc_dedupe(e, S);
+        bad |= dalloc(e, E.leaf_net, S + 16);
         if (bad) return fail(XQ_E_HIP, "hipMalloc failed while sizing the pending-leaf slots");
-        E.leaf_slots = K;
+        E.leaf_slots = K; E.n_slots = (int)S;
         HIPCHK(hipMemsetAsync(E.leaf_node, 0xff, S * 2, e->stream));        // LEAF_NONE
     }
     E.vloss = enable ? 1 : 0;
@@ -2489,13 +2577,28 @@ extern "C" int xq_engine_set_search_stamps(void *dev_u64x16_per_game)
 #endif
 }
 
-extern "C" int xq_engine_search_round(xq_engine *e, int round, int eval_kind, const void *ev_a, const void *ev_v,
-                                      void *planes)
+// a two-network round needs what a second network always needed: no evaluation cache (its key is the position alone) and
+// no root evaluation carry-over (the carried priors are the mover's network's)
+static int two_net_ok(xq_engine *e)
+{
+    if (e->E.ec_on || e->ec_want) return fail(XQ_E_INVALID, "a two-network round cannot use the evaluation cache (two networks answer differently for one position): xq_engine_set_eval_cache(e, 0)");
+    if (e->E.eval_carry) return fail(XQ_E_INVALID, "a two-network round cannot use the root evaluation carry-over (the carried priors are the mover's network's)");
+    return 0;
+}
+
+// one search round; two = 1: per-slot network selection (the second triple answers the leaves of network 1)
+static int search_round_impl(xq_engine *e, int round, int eval_kind, const void *ev_a, const void *ev_v, int eval_kind1,
+                             const void *ev_a1, const void *ev_v1, void *planes, int two)
 {
     if (!e) return fail(XQ_E_INVALID, "null engine");
     if (round < 0 || round >= e->E.nrounds) return fail(XQ_E_INVALID, "round out of range");
     if (eval_kind < XQ_EVAL_PRIORS || eval_kind > XQ_EVAL_LOGITS_BF16) return fail(XQ_E_INVALID, "bad eval_kind");
-    if (round > 0 && (!ev_a || !ev_v)) return fail(XQ_E_INVALID, "evaluator output missing");
+    if (eval_kind1 < XQ_EVAL_PRIORS || eval_kind1 > XQ_EVAL_LOGITS_BF16) return fail(XQ_E_INVALID, "bad eval_kind");
+    if (round > 0 && (!ev_a || !ev_v || !ev_a1 || !ev_v1)) return fail(XQ_E_INVALID, "evaluator output missing");
+    if (two) { if (int rc = two_net_ok(e)) return rc; }
+    if (eval_kind1 != XQ_EVAL_PRIORS && ev_a1 && e->E.compact && !e->row_map_fetched)
+        return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map_net (rows are compacted)");
+    e->E.two_net = two ? 1 : 0;
     if (!planes_ok(e->cfg.planes_format)) return fail(XQ_E_INVALID, "bad planes_format");
     if (eval_kind != XQ_EVAL_PRIORS && ev_a && e->E.compact && !e->row_map_fetched)
         return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map (rows are compacted) "
@@ -2510,6 +2613,7 @@ extern "C" int xq_engine_search_round(xq_engine *e, int round, int eval_kind, co
         if (ev) HIPCHK(hipEventRecord(ev->first, e->stream));
     }
     const int fmt = planes ? e->cfg.planes_format : XQ_PLANES_NONE;
+    const EvalPair evp{ { { ev_a, ev_v, eval_kind, 0 }, { ev_a1, ev_v1, eval_kind1, 0 } } };
     e->E.ec_epoch = e->ec_epoch; e->E.ec_seq = ++e->ec_seq;
     if (e->E.dedupe) {                                                    // a fresh tag for this round's table entries
         if (++e->dd_tag == 0) {                                           // tag wrap: start from a cleared table
@@ -2519,12 +2623,12 @@ extern "C" int xq_engine_search_round(xq_engine *e, int round, int eval_kind, co
         e->E.dd_tag = e->dd_tag;
     }
 #define XQ_LAUNCH_SEARCH(OCC, VLB) hipLaunchKernelGGL((k_search_round<OCC, VLB>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, \
-                                                    round, batch, eval_kind, ev_a, ev_v, planes, fmt, (unsigned long long *)nullptr)
+                                                    round, batch, evp, planes, fmt, (unsigned long long *)nullptr)
     if (e->E.vloss) XQ_LAUNCH_SEARCH(4, true);
 #if XQ_TOWER_PROBES
     else if (g_search_stamps)
-        hipLaunchKernelGGL((k_search_round<4, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, eval_kind,
-                           ev_a, ev_v, planes, fmt, (unsigned long long *)g_search_stamps);
+        hipLaunchKernelGGL((k_search_round<4, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
+                           planes, fmt, (unsigned long long *)g_search_stamps);
 #endif
     else switch (g_search_occ) {
 #if XQ_TOWER_PROBES                 // the other register budgets spill 27-58 VGPRs: comparison builds, probes library only
@@ -2545,6 +2649,18 @@ extern "C" int xq_engine_search_round(xq_engine *e, int round, int eval_kind, co
         e->row_seq++;
     }
     return 0;
+}
+
+extern "C" int xq_engine_search_round(xq_engine *e, int round, int eval_kind, const void *ev_a, const void *ev_v,
+                                      void *planes)
+{
+    return search_round_impl(e, round, eval_kind, ev_a, ev_v, eval_kind, ev_a, ev_v, planes, 0);
+}
+
+extern "C" int xq_engine_search_round2(xq_engine *e, int round, int eval_kind0, const void *ev_a0, const void *ev_v0,
+                                       int eval_kind1, const void *ev_a1, const void *ev_v1, void *planes)
+{
+    return search_round_impl(e, round, eval_kind0, ev_a0, ev_v0, eval_kind1, ev_a1, ev_v1, planes, 1);
 }
 
 // Evaluator row compaction (default off: row = slot, every slot is evaluated).  When on, every search round is
@@ -2629,18 +2745,24 @@ extern "C" int xq_engine_eval_cache_stats(xq_engine *e, uint64_t *hits_fills_hos
     return 0;
 }
 
-extern "C" int xq_engine_row_map(xq_engine *e, const int32_t **row_src_dev, const int32_t **row_count_dev)
+extern "C" int xq_engine_row_map_net(xq_engine *e, int net, const int32_t **row_src_dev, const int32_t **row_count_dev)
 {
     if (!e || !row_src_dev || !row_count_dev) return fail(XQ_E_INVALID, "null argument");
+    if (net < 0 || net > 1) return fail(XQ_E_INVALID, "net must be 0 or 1");
     e->row_map_fetched = true;
-    *row_src_dev = e->E.compact ? e->E.row_src : nullptr;
-    *row_count_dev = e->E.compact ? e->E.row_count : nullptr;
+    *row_src_dev = e->E.compact ? e->E.row_src + (size_t)net * e->E.n_slots : nullptr;
+    *row_count_dev = e->E.compact ? e->E.row_count + net : nullptr;
     return 0;
+}
+
+extern "C" int xq_engine_row_map(xq_engine *e, const int32_t **row_src_dev, const int32_t **row_count_dev)
+{
+    return xq_engine_row_map_net(e, 0, row_src_dev, row_count_dev);
 }
 
 // rows of the last `cap` search rounds (oldest first) and the number of rounds launched since the engine was
 // created or the history was last reset (reset != 0 restarts the count after reading)
-extern "C" int xq_engine_read_row_history(xq_engine *e, int32_t *rows, int cap, int64_t *n_rounds, int reset)
+static int read_row_history_from(xq_engine *e, const int32_t *ring_dev, int32_t *rows, int cap, int64_t *n_rounds, int reset)
 {
     if (!e || !n_rounds || cap < 0 || (cap > 0 && !rows)) return fail(XQ_E_INVALID, "bad argument");
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -2651,11 +2773,23 @@ extern "C" int xq_engine_read_row_history(xq_engine *e, int32_t *rows, int cap, 
     if (take > ROW_HIST) take = ROW_HIST;
     if (take > 0) {
         std::vector<int32_t> ring(ROW_HIST);
-        HIPCHK(hipMemcpy(ring.data(), e->E.row_hist, (size_t)ROW_HIST * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ring.data(), ring_dev, (size_t)ROW_HIST * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < take; i++) rows[i] = ring[(n - (unsigned)take + (unsigned)i) & (ROW_HIST - 1)];
     }
     if (reset) e->row_seq = 0;
     return 0;
+}
+
+extern "C" int xq_engine_read_row_history(xq_engine *e, int32_t *rows, int cap, int64_t *n_rounds, int reset)
+{
+    if (!e) return fail(XQ_E_INVALID, "bad argument");
+    return read_row_history_from(e, e->E.row_hist, rows, cap, n_rounds, reset);
+}
+
+extern "C" int xq_engine_read_row_history_net(xq_engine *e, int net, int32_t *rows, int cap, int64_t *n_rounds, int reset)
+{
+    if (!e || net < 0 || net > 1) return fail(XQ_E_INVALID, "bad argument");
+    return read_row_history_from(e, e->E.row_hist_net + (size_t)net * ROW_HIST, rows, cap, n_rounds, reset);
 }
 
 extern "C" int xq_engine_read_leaf_rows(xq_engine *e, int32_t *rows /*[G * leaf_slots]*/)
@@ -2669,26 +2803,44 @@ extern "C" int xq_engine_read_leaf_rows(xq_engine *e, int32_t *rows /*[G * leaf_
     return 0;
 }
 
-extern "C" int xq_engine_eval_hashnet(xq_engine *e, int salt)
+extern "C" int xq_engine_eval_hashnet2(xq_engine *e, int salt0, int salt1)
 {
     if (!e) return fail(XQ_E_INVALID, "null engine");
     HIPCHK(hipSetDevice(e->cfg.device));
-    hipLaunchKernelGGL(k_hashnet, dim3(e->E.G * e->E.leaf_slots), dim3(64), 0, e->stream, e->E, salt);
+    hipLaunchKernelGGL(k_hashnet, dim3(e->E.G * e->E.leaf_slots), dim3(64), 0, e->stream, e->E, salt0, salt1);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int xq_engine_eval_hashnet(xq_engine *e, int salt) { return xq_engine_eval_hashnet2(e, salt, salt); }
+
+static int end_search_impl(xq_engine *e, int eval_kind, const void *ev_a, const void *ev_v, int eval_kind1, const void *ev_a1,
+                           const void *ev_v1, int two)
+{
+    if (!e || !ev_a || !ev_v || !ev_a1 || !ev_v1) return fail(XQ_E_INVALID, "null argument");
+    if (eval_kind < XQ_EVAL_PRIORS || eval_kind > XQ_EVAL_LOGITS_BF16) return fail(XQ_E_INVALID, "bad eval_kind");
+    if (eval_kind1 < XQ_EVAL_PRIORS || eval_kind1 > XQ_EVAL_LOGITS_BF16) return fail(XQ_E_INVALID, "bad eval_kind");
+    if ((eval_kind != XQ_EVAL_PRIORS || eval_kind1 != XQ_EVAL_PRIORS) && e->E.compact && !e->row_map_fetched)
+        return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map or switch it off");
+    if (two) { if (int rc = two_net_ok(e)) return rc; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    e->E.two_net = two ? 1 : 0;
+    e->E.ec_epoch = e->ec_epoch; e->E.ec_seq = ++e->ec_seq;
+    const EvalPair evp{ { { ev_a, ev_v, eval_kind, 0 }, { ev_a1, ev_v1, eval_kind1, 0 } } };
+    hipLaunchKernelGGL(k_end_search, dim3(e->E.G), dim3(64), 0, e->stream, e->E, evp);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int xq_engine_end_search(xq_engine *e, int eval_kind, const void *ev_a, const void *ev_v)
 {
-    if (!e || !ev_a || !ev_v) return fail(XQ_E_INVALID, "null argument");
-    if (eval_kind < XQ_EVAL_PRIORS || eval_kind > XQ_EVAL_LOGITS_BF16) return fail(XQ_E_INVALID, "bad eval_kind");
-    if (eval_kind != XQ_EVAL_PRIORS && e->E.compact && !e->row_map_fetched)
-        return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map or switch it off");
-    HIPCHK(hipSetDevice(e->cfg.device));
-    e->E.ec_epoch = e->ec_epoch; e->E.ec_seq = ++e->ec_seq;
-    hipLaunchKernelGGL(k_end_search, dim3(e->E.G), dim3(64), 0, e->stream, e->E, eval_kind, ev_a, ev_v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return end_search_impl(e, eval_kind, ev_a, ev_v, eval_kind, ev_a, ev_v, 0);
+}
+
+extern "C" int xq_engine_end_search2(xq_engine *e, int eval_kind0, const void *ev_a0, const void *ev_v0, int eval_kind1,
+                                     const void *ev_a1, const void *ev_v1)
+{
+    return end_search_impl(e, eval_kind0, ev_a0, ev_v0, eval_kind1, ev_a1, ev_v1, 1);
 }
 
 extern "C" int xq_engine_play_move(xq_engine *e)
@@ -2752,17 +2904,30 @@ extern "C" int xq_engine_finalize(xq_engine *e)
     return 0;
 }
 
-extern "C" int xq_engine_refill_begin(xq_engine *e, const uint32_t *seeds, int total)
+// pairing (by game id, or NULL: the session default - cfg.opponent_mode - for every game): slots of a refill session are at
+// different plies, so a session with a pairing-1 game must be searched with xq_engine_search_round2 / end_search2, which
+// choose the mover's network per slot on the device.
+extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int total, const uint8_t *pairing)
 {
     if (!e || !seeds) return fail(XQ_E_INVALID, "null argument");
     if (total < e->E.G) return fail(XQ_E_INVALID, "refill needs at least as many games as slots");
-    if (e->E.opponent_mode) return fail(XQ_E_INVALID, "refill is not available in opponent (arena) mode: slots are at different plies");
+    bool second = pairing ? false : e->E.opponent_mode != 0;
+    if (pairing)
+        for (int i = 0; i < total; i++) {
+            if (pairing[i] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
+            second |= pairing[i] != 0;
+        }
+    if (second && (e->E.eval_carry || e->ec_want))
+        return fail(XQ_E_INVALID, "a refill session with a second network cannot use the evaluation cache or the root evaluation carry-over");
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t G = (size_t)e->E.G, T = (size_t)total;
     if (total > e->refill_cap) {             // (buffers of an earlier, smaller session stay in e->allocs until destroy)
-        if (dalloc(e, e->uni_all, T * XQ_MAX_PLIES) || dalloc(e, e->out_gs, T)) return fail(XQ_E_HIP, "hipMalloc failed");
+        if (dalloc(e, e->uni_all, T * XQ_MAX_PLIES) || dalloc(e, e->out_gs, T) || dalloc(e, e->pair_all, T))
+            return fail(XQ_E_HIP, "hipMalloc failed");
         e->refill_cap = total;
     }
+    e->refill_pairs = pairing != nullptr;
+    if (pairing) HIPCHK(hipMemcpyAsync(e->pair_all, pairing, T, hipMemcpyHostToDevice, e->stream));   // (drained below)
     e->refill_total = total;                 // the session's size, every session: k_refill deals game ids below it only
     if (!e->slot_game && (dalloc(e, e->slot_game, G) || dalloc(e, e->next_game, (size_t)1)))
         return fail(XQ_E_HIP, "hipMalloc failed");
@@ -2784,6 +2949,38 @@ extern "C" int xq_engine_refill_begin(xq_engine *e, const uint32_t *seeds, int t
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
     hipLaunchKernelGGL(k_new_games, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());
+    // the first G games sit in slot = id (k_new_games gave them what lock-step games get)
+    if (pairing) HIPCHK(hipMemcpyAsync(e->E.pairing, e->pair_all, G, hipMemcpyDeviceToDevice, e->stream));
+    else HIPCHK(hipMemsetAsync(e->E.pairing, e->E.opponent_mode ? 1 : 0, G, e->stream));
+    return 0;
+}
+
+// (the old entry point: every game gets the session default; it never needed the opponent-mode refusal for itself - the
+// refusal was about the host choosing the network by ply, which search_round2 no longer does)
+extern "C" int xq_engine_refill_begin(xq_engine *e, const uint32_t *seeds, int total)
+{
+    return xq_engine_refill_begin2(e, seeds, total, nullptr);
+}
+
+// Per-slot pairing of lock-step / set_roots sessions: pairing_host[g] for the game in slot g, now and for the games
+// xq_engine_new_games starts later; NULL = back to the session default (cfg.opponent_mode everywhere).
+extern "C" int xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing)
+{
+    if (!e) return fail(XQ_E_INVALID, "null engine");
+    const size_t G = (size_t)e->E.G;
+    bool second = pairing ? false : e->E.opponent_mode != 0;
+    if (pairing)
+        for (size_t g = 0; g < G; g++) {
+            if (pairing[g] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
+            second |= pairing[g] != 0;
+        }
+    if (second && (e->E.eval_carry || e->ec_want))
+        return fail(XQ_E_INVALID, "a second network cannot be combined with the evaluation cache or the root evaluation carry-over");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (pairing) HIPCHK(hipMemcpyAsync(e->pairing_init, pairing, G, hipMemcpyHostToDevice, e->stream));
+    else HIPCHK(hipMemsetAsync(e->pairing_init, e->E.opponent_mode ? 1 : 0, G, e->stream));
+    HIPCHK(hipMemcpyAsync(e->E.pairing, e->pairing_init, G, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));          // (the caller's array may go away)
     return 0;
 }
 
@@ -2793,7 +2990,8 @@ extern "C" int xq_engine_refill_step(xq_engine *e, void *records, int32_t *activ
     if (!e->slot_game || e->refill_total <= 0) return fail(XQ_E_INVALID, "xq_engine_refill_begin first");
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemsetAsync(e->active_dev, 0, 4, e->stream));
-    Refill R{ e->uni_all, e->slot_game, e->next_game, e->active_dev, e->out_gs, (xq_sample_record *)records, e->refill_total };
+    Refill R{ e->uni_all, e->slot_game, e->next_game, e->active_dev, e->out_gs, (xq_sample_record *)records, e->refill_total,
+              e->refill_pairs ? e->pair_all : nullptr, e->E.opponent_mode ? 1 : 0 };
     hipLaunchKernelGGL(k_refill, dim3(e->E.G), dim3(64), 0, e->stream, e->E, R);
     HIPCHK(hipGetLastError());
     if (active) {

@@ -187,8 +187,12 @@ def weights_equal_across_ranks(tensors, group=None, device=None):
     return bool(torch.equal(lo, hi))
 
 
-def play_sharded(make_evaluator, num_games, sims, base_seed=0, temperature=1.0, group=None, gather=True, network=None):
+def play_sharded(make_evaluator, num_games, sims, base_seed=0, temperature=1.0, group=None, gather=True, network=None,
+                 opponent_network=None, make_opponent_evaluator=None):
     """Each rank plays its shard on its own GPU, then all ranks all-gather the sample records.
+    `opponent_network` / `make_opponent_evaluator`: the shard's games are `network` red vs the opponent black, red
+    plies stored only (self_play.py:190-198, 211, 234); the opponent's weights are broadcast like the first network's,
+    one broadcast_weights each.
     `network` (a ChessNet on this rank's GPU): rank 0's weights are broadcast to every rank first
     (broadcast_weights: what parallel_self_play's per-task state_dict does, self_play.py:386-394) and every rank
     builds its leaf evaluator from them; `make_evaluator` may then be None.  Without `network` the caller's
@@ -210,11 +214,17 @@ def play_sharded(make_evaluator, num_games, sims, base_seed=0, temperature=1.0, 
         ev = make_evaluator() if make_evaluator is not None else TorchNetEvaluator(network)
     else:
         ev = make_evaluator()
-    eng = SelfPlayEngine(n_local, sims=sims, temperature=temperature,
+    ev_b = None
+    if opponent_network is not None:
+        broadcast_weights(opponent_network, src=0, group=group)
+        ev_b = make_opponent_evaluator() if make_opponent_evaluator is not None else TorchNetEvaluator(opponent_network)
+    elif make_opponent_evaluator is not None:
+        ev_b = make_opponent_evaluator()
+    eng = SelfPlayEngine(n_local, sims=sims, temperature=temperature, opponent_mode=ev_b is not None,
                          planes_format=getattr(ev, "planes_format", _lib.PLANES_NONE),
                          device=torch.cuda.current_device(),
                          stream=torch.cuda.current_stream().cuda_stream)
-    eng.play(ev, game_seeds(base_seed, num_games, rank, world), read=False)
+    eng.play(ev, game_seeds(base_seed, num_games, rank, world), opponent_evaluator=ev_b, read=False)
     local = torch.zeros(n_pad * _lib.MAX_PLIES * RECORD_BYTES, dtype=torch.uint8, device="cuda")
     eng.pack_samples(local.data_ptr())
     gathered = all_gather_records(local, group) if gather else None

@@ -18,6 +18,31 @@ from . import _lib
 from .chess_env import decode_move, format_end_reason
 
 
+def check_per_slot_evaluators(evaluator, opponent_evaluator):
+    """What a per-slot (two-network) session cannot serve, said before any device call: a CallbackEvaluator reads its
+    rows through xq_engine_read_leaves, which does not say which network a leaf waits for."""
+    for ev in (evaluator, opponent_evaluator):
+        if isinstance(ev, CallbackEvaluator):
+            raise _lib.XqError("a CallbackEvaluator cannot take part in a per-slot two-network session (read_leaves does not "
+                               "carry the leaf's network): use HashNetEvaluator / TorchNetEvaluator, or the lock-step play()")
+
+
+def normalise_pairing(pairing, total, has_opponent):
+    """The pairing array of `total` games as uint8 (None: all 1 with an opponent, else None = the engine's default).
+    Raises ValueError for a wrong length, a value other than 0 / 1, or a pairing-1 game without an opponent."""
+    if pairing is None:
+        return np.ones(total, np.uint8) if has_opponent else None
+    p = np.ascontiguousarray(pairing)
+    if p.shape != (total,):
+        raise ValueError("pairing must hold one entry per game: expected %d, got shape %s" % (total, p.shape))
+    if not np.isin(p, (0, 1)).all():
+        raise ValueError("pairing entries are 0 (self-play) or 1 (network 0 red vs network 1 black)")
+    p = p.astype(np.uint8)
+    if p.any() and not has_opponent:
+        raise ValueError("a pairing-1 game needs an opponent evaluator")
+    return p
+
+
 class HashNetEvaluator:
     """SURVEY.md Appendix B evaluator, on the GPU."""
     planes_format = _lib.PLANES_NONE
@@ -128,7 +153,10 @@ class TorchNetEvaluator:
         self._rounds_at_bind = 0
         self.row_src = self.n_rows_dev = None
 
-    def bind(self, engine):
+    def bind(self, engine, net=0, planes_of=None):
+        """net = 1: bound as network 1 of a per-slot session (SelfPlayEngine.search(..., per_slot=True)): rows by
+        row_map_net(1), own logits / values, and the input planes the search kernel wrote into `planes_of`'s storage -
+        network 0's - which are written once (without `planes_of`, e.g. beside a HashNetEvaluator, it owns them)."""
         torch = self.torch
         engine.set_row_compaction(self.row_compaction)
         if self.row_compaction:
@@ -138,9 +166,11 @@ class TorchNetEvaluator:
             if use:
                 engine.eval_cache_stats(reset=True)
                 self._rounds_at_bind = engine.row_history(cap=0)[1]
-        self.row_src, self.n_rows_dev = engine.row_map()
+        self.row_src, self.n_rows_dev = engine.row_map_net(net) if net else engine.row_map()
         G = engine.n_rows                                       # one row per pending-leaf slot
-        if self.channels_last:
+        if planes_of is not None:
+            self.storage, self.x = planes_of.storage, planes_of.x
+        elif self.channels_last:
             self.storage = torch.zeros((G, 10, 9, 16), dtype=self.dtype, device="cuda")
             self.x = self.storage.permute(0, 3, 1, 2)            # logical NCHW, channels-last strides
         else:
@@ -381,6 +411,30 @@ class SelfPlayEngine:
         _lib.check(self.L.xq_engine_read_row_history(self.h, _lib.ptr(rows), cap, C.byref(n), 1 if reset else 0))
         return rows[:min(cap, n.value)], n.value
 
+    def row_map_net(self, net):
+        """row_map() of one network of a per-slot session (rows in slot order within each network; row_src of either
+        network indexes the one set of planes the search kernel writes)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        _lib.check(self.L.xq_engine_row_map_net(self.h, int(net), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def row_history_net(self, net, cap=65536):
+        """row_history() of one network: the rows that network's evaluator had to run in each of the last rounds (a
+        single-network round counts as network 0's)."""
+        cap = min(int(cap), _lib.ROW_HISTORY)
+        rows = np.zeros(cap, np.int32)
+        n = C.c_int64()
+        _lib.check(self.L.xq_engine_read_row_history_net(self.h, int(net), _lib.ptr(rows), cap, C.byref(n), 0))
+        return rows[:min(cap, n.value)], n.value
+
+    def set_pairing(self, pairing=None):
+        """Per-slot pairing of a lock-step / set_roots session: pairing[g] = 0 network 0 moves both sides of the game in
+        slot g, 1 = network 0 is red and network 1 black (None: back to the engine's default, 1 everywhere for an
+        opponent_mode engine, else 0).  Holds for the games in the slots now and for later new_games()."""
+        if pairing is not None:
+            pairing = normalise_pairing(pairing, self.n_games, True)
+        _lib.check(self.L.xq_engine_set_pairing(self.h, _lib.ptr(pairing)))
+
     def leaf_rows(self):
         rows = np.zeros(self.n_rows, np.int32)
         _lib.check(self.L.xq_engine_read_leaf_rows(self.h, _lib.ptr(rows)))
@@ -391,10 +445,35 @@ class SelfPlayEngine:
         _lib.check(self.L.xq_engine_roots_not_ready(self.h, _lib.ptr(n)))
         return int(n[0])
 
-    def search(self, evaluator, skip_round0=False):
+    def _evaluate_pair(self, ev0, ev1):
+        if isinstance(ev0, HashNetEvaluator) and isinstance(ev1, HashNetEvaluator):
+            # one launch: every pending leaf with the salt of its own network, by slot in the one priors / values array
+            _lib.check(self.L.xq_engine_eval_hashnet2(self.h, ev0.salt, ev1.salt))
+            t = (_lib.EVAL_PRIORS, self.priors_ptr, self.values_ptr)
+            return t, t
+        return ev0.evaluate(self), ev1.evaluate(self)
+
+    def search(self, evaluator, opponent_evaluator=None, per_slot=False, skip_round0=False):
         """One MCTS.search for every game (self_play.py:89-154); root visits are final after it.
         skip_round0: every root already holds its expansion (set_root_eval_carry + roots_not_ready() == 0); with row
-        compaction nobody needs to know: a carried root simply has no row in round 0."""
+        compaction nobody needs to know: a carried root simply has no row in round 0.
+        per_slot: two networks, chosen per slot on the device (set_pairing / play_refill(pairing=...)): a slot's ply is
+        searched with the network of the side to move at its root - `evaluator` (network 0) unless the game's pairing is 1
+        and black is to move, then `opponent_evaluator` (network 1).  Each round runs the tree kernel, then BOTH evaluators,
+        each on the rows of its own network.  The evaluation cache and the root evaluation carry-over are off in such a
+        session, for its self-play slots too.  Both evaluators must have been bound (play_refill does; else _bind(ev0, ev1,
+        per_slot=True))."""
+        if per_slot:
+            if opponent_evaluator is None:
+                raise _lib.XqError("search(per_slot=True) needs both evaluators")
+            check_per_slot_evaluators(evaluator, opponent_evaluator)
+            t0 = t1 = (_lib.EVAL_PRIORS, None, None)
+            pp = evaluator.planes_ptr() or opponent_evaluator.planes_ptr()
+            for r in range(self.rounds):
+                _lib.check(self.L.xq_engine_search_round2(self.h, r, t0[0], t0[1], t0[2], t1[0], t1[1], t1[2], pp))
+                t0, t1 = self._evaluate_pair(evaluator, opponent_evaluator)
+            _lib.check(self.L.xq_engine_end_search2(self.h, t0[0], t0[1], t0[2], t1[0], t1[1], t1[2]))
+            return
         kind, a, v = _lib.EVAL_PRIORS, None, None
         if skip_round0:
             a, v = self.priors_ptr, self.values_ptr          # nothing is pending: round 1 has nothing to consume
@@ -506,7 +585,7 @@ class SelfPlayEngine:
         return (bool(getattr(ev, "row_compaction", False)), bool(getattr(ev, "leaf_dedupe", False)),
                 getattr(inet, "n_policy", None))
 
-    def _bind(self, evaluator, opponent_evaluator=None):
+    def _bind(self, evaluator, opponent_evaluator=None, per_slot=False):
         """Bind the evaluator(s) of the games about to start.  The engine's row layout is reset first: an evaluator that
         hands its logits in by slot (no `row_compaction` attribute) must never meet the compaction an earlier
         TorchNetEvaluator.bind left behind (the C side refuses that combination too); those that want compaction switch
@@ -523,7 +602,11 @@ class SelfPlayEngine:
                 ev.bind(self)                 # (by-slot priors first: they do not touch the layout)
         for ev in (evaluator, opponent_evaluator):
             if ev is not None and self._row_layout(ev) is not None:
-                ev.bind(self)
+                if per_slot and ev is opponent_evaluator and isinstance(ev, TorchNetEvaluator):
+                    # network 1 of a per-slot session: its own rows and outputs, network 0's planes
+                    ev.bind(self, net=1, planes_of=evaluator if isinstance(evaluator, TorchNetEvaluator) else None)
+                else:
+                    ev.bind(self)
         if opponent_evaluator is not None:
             self.set_eval_cache(False)        # two networks answer differently for one position
 
@@ -562,23 +645,35 @@ class SelfPlayEngine:
                 ev.after_play(self)
         return self.read_results() if read else None
 
-    def play_refill(self, evaluator, seeds, records_ptr, check_every=4, max_plies=None, on_ply=None):
+    def play_refill(self, evaluator, seeds, records_ptr, check_every=4, max_plies=None, on_ply=None,
+                    opponent_evaluator=None, pairing=None):
         """`len(seeds)` games through the engine's G slots with refill (xq_engine_refill_*): a finished game's
         slot restarts on the next unplayed seed at once, like the reference's pool (self_play.py:404-408).
         `records_ptr`: device buffer of len(seeds) * 70 sample records (distributed.RECORD_BYTES each), filled
         by game id.  Returns the per-game outcome arrays (by game id) and the number of plies stepped.
-        `on_ply(ply)`: called after every refill step (tests / monitoring; reading engine state there synchronises)."""
+        `on_ply(ply)`: called after every refill step (tests / monitoring; reading engine state there synchronises).
+        `opponent_evaluator` (network 1) + `pairing` (by game id: 0 = self-play of `evaluator`, 1 = `evaluator` red vs the
+        opponent black, red plies stored only - self_play.py:190-198, 211, 234; default all 1): the reference trainer's
+        two halves of an epoch (trainer.py:186-209) in ONE session - the mover's network is chosen per slot on the device
+        (search(per_slot=True)), so slots may be at any ply.  Such a session runs without the evaluation cache and the
+        root evaluation carry-over, its self-play slots included."""
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         total = len(seeds)
-        carry = self._auto_carry(evaluator, None)
-        self._bind(evaluator)
-        _lib.check(self.L.xq_engine_refill_begin(self.h, _lib.ptr(seeds), total))
+        two = opponent_evaluator is not None
+        pairing = normalise_pairing(pairing, total, two)
+        if two:
+            check_per_slot_evaluators(evaluator, opponent_evaluator)
+        elif self.opponent_mode:
+            raise _lib.XqError("play_refill on an opponent-mode engine needs opponent_evaluator")
+        carry = self._auto_carry(evaluator, opponent_evaluator)
+        self._bind(evaluator, opponent_evaluator, per_slot=two)
+        _lib.check(self.L.xq_engine_refill_begin2(self.h, _lib.ptr(seeds), total, _lib.ptr(pairing)))
         active = np.zeros(1, np.int32)
         plies = 0
         cap = max_plies or (total // self.n_games + 2) * _lib.MAX_PLIES + 8
         skip0 = False
         while plies < cap:
-            self.search(evaluator, skip_round0=skip0)
+            self.search(evaluator, opponent_evaluator, per_slot=two, skip_round0=skip0)
             _lib.check(self.L.xq_engine_play_move(self.h))
             poll = plies % check_every == check_every - 1
             _lib.check(self.L.xq_engine_refill_step(self.h, C.c_void_p(records_ptr), _lib.ptr(active) if poll else None))
@@ -590,8 +685,9 @@ class SelfPlayEngine:
                 break
         else:
             raise _lib.XqError("play_refill: games still active after %d plies" % cap)
-        if hasattr(evaluator, "after_play"):
-            evaluator.after_play(self)
+        for ev in (evaluator, opponent_evaluator):
+            if ev is not None and hasattr(ev, "after_play"):
+                ev.after_play(self)
         out = {k: np.zeros(total, np.int32) for k in ("winner", "reason", "reason_side", "reason_count", "n_plies",
                                                       "n_samples", "error")}
         _lib.check(self.L.xq_engine_refill_read_games(self.h, *[_lib.ptr(out[k]) for k in (

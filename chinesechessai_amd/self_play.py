@@ -11,9 +11,10 @@ import math
 import numpy as np
 
 from . import _lib
-from .chess_env import ChineseChess, decode_move, _sq
+from .chess_env import ChineseChess, decode_move, format_end_reason, _sq
 from .config import MAX_MOVES, MCTS_SIMULATIONS
-from .engine import CallbackEvaluator, HashNetEvaluator, SelfPlayEngine, TorchNetEvaluator
+from .engine import (CallbackEvaluator, HashNetEvaluator, SelfPlayEngine, TorchNetEvaluator, check_per_slot_evaluators,
+                     normalise_pairing)
 
 
 class InterruptedWithResults(Exception):
@@ -239,6 +240,68 @@ def parallel_self_play(network, num_games, temperature=1.0, num_simulations=None
     batch = _play_batch(network, num_games, temperature, num_simulations, opponent_network, seeds=seeds,
                         inference_dtype=inference_dtype, partial_on_interrupt=True)
     return batch.results()
+
+
+def epoch_pairing(num_games, has_opponent):
+    """Pairing by game id of one epoch as the reference trainer mixes it (trainer.py:156-163): the first
+    num_games // 2 games are self-play (0), the rest new model red vs old model black (1); all self-play without an
+    old model."""
+    p = np.zeros(num_games, np.uint8)
+    if has_opponent:
+        p[num_games // 2:] = 1
+    return p
+
+
+def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, opponent_network=None, slots=None,
+                    seeds=None):
+    """The self-play of one trainer epoch (trainer.py:186-209: parallel_self_play(model, num_games // 2) and then
+    parallel_self_play(model, num_games - num_games // 2, opponent_network=old_model)) in ONE refill session: both
+    kinds of game go through the same `slots` concurrent slots and a finished game's slot takes the next game at once,
+    whichever kind (self_play.py:404-408).  Game ids below num_games // 2 are self-play, the rest are `network` red vs
+    `opponent_network` black and hold red plies only (self_play.py:234); without an opponent every game is self-play.
+    Returns [(game_data, winner, end_reason)] in game-id order, each entry what parallel_self_play returns for that
+    game's seed (failed games are dropped as there).  `seeds`: one per game (default: drawn from np.random)."""
+    num_games = int(num_games)
+    if num_games < 1:
+        raise ValueError("self_play_epoch: num_games must be at least 1")
+    slots = num_games if slots is None else int(slots)
+    if slots < 1:
+        raise ValueError("self_play_epoch: slots must be at least 1")
+    slots = min(slots, num_games)
+    if seeds is None:
+        seeds = np.random.randint(0, 2 ** 31 - 1, size=num_games).astype(np.uint32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    if seeds.shape != (num_games,):
+        raise ValueError("self_play_epoch: seeds must hold one entry per game")
+    two = opponent_network is not None
+    pairing = normalise_pairing(epoch_pairing(num_games, two), num_games, two) if two else None
+    ev = _evaluator_for(network)
+    ev_b = _evaluator_for(opponent_network) if two else None
+    if two:
+        check_per_slot_evaluators(ev, ev_b)
+        if getattr(ev_b, "planes_format", 0) != getattr(ev, "planes_format", 0):
+            raise ValueError("both networks must use the same planes format")
+    sims = num_simulations if num_simulations else MCTS_SIMULATIONS
+    # ---- everything above is argument handling: the device is first touched here
+    import torch
+    from .distributed import RECORD_BYTES, record_to_sample, records_to_numpy
+    eng = SelfPlayEngine(slots, sims=sims, temperature=temperature, max_moves=MAX_MOVES,
+                         planes_format=getattr(ev, "planes_format", _lib.PLANES_NONE))
+    try:
+        records = torch.zeros(num_games * _lib.MAX_PLIES * RECORD_BYTES, dtype=torch.uint8, device="cuda")
+        out, _ = eng.play_refill(ev, seeds, records.data_ptr(), opponent_evaluator=ev_b, pairing=pairing)
+        torch.cuda.synchronize()
+        rec = records_to_numpy(records).reshape(num_games, _lib.MAX_PLIES)
+    finally:
+        eng.close()
+    results = []
+    for g in range(num_games):
+        if out["error"][g]:
+            continue
+        data = [record_to_sample(rec[g, i], temperature) for i in range(int(out["n_samples"][g]))]
+        reason = format_end_reason(int(out["reason"][g]), int(out["reason_side"][g]), int(out["reason_count"][g]))
+        results.append((data, int(out["winner"][g]), reason if reason else "未知原因"))
+    return results
 
 
 class SelfPlay:

@@ -338,8 +338,8 @@ int  xq_engine_eval_cache_stats(xq_engine *e, uint64_t *hits_fills_mismatches_ho
  * xq_engine_refill_step } until *active_host reads 0.  refill_step retires every finished game into
  * records_dev[id][0..69] (z table applied, self_play.py:259-310) and its outcome into the table
  * refill_read_games returns (same fields as xq_engine_read_games, indexed by game id 0..total-1), and
- * restarts the slot.  active_host may be NULL (no host synchronisation in that step).  total >= G; not
- * available in opponent mode (slots are at different plies). */
+ * restarts the slot.  active_host may be NULL (no host synchronisation in that step).  total >= G.  Slots
+ * are at different plies: a session with a second network is searched with xq_engine_search_round2 (below). */
 int  xq_engine_refill_begin(xq_engine *e, const uint32_t *seeds_host /*[total]*/, int total);
 int  xq_engine_refill_step(xq_engine *e, void *records_dev /* xq_sample_record[total][70] */, int32_t *active_host);
 int  xq_engine_refill_read_games(xq_engine *e, int32_t *winner, int32_t *reason, int32_t *reason_side,
@@ -348,6 +348,35 @@ int  xq_engine_refill_read_games(xq_engine *e, int32_t *winner, int32_t *reason,
  * slots that finish in the same step gets which id is not specified (an atomic counter deals them); a game's
  * result does not depend on it. */
 int  xq_engine_refill_read_slots(xq_engine *e, int32_t *slot_game_host /*[G]*/);
+
+/* ---- two networks, chosen per slot on the device.  The reference trainer plays half of an epoch's games as "new model
+ * red vs frozen old model black" (trainer.py:186-209, self_play.py:190-198, 211) through the same pool as its self-play
+ * games.  A game's PAIRING is 0 (network 0 moves both sides) or 1 (network 0 is red, network 1 black); the network of a
+ * slot for a ply is the network of the side to move at the root (side == red || pairing == 0 ? 0 : 1), and the whole tree
+ * of that ply is searched with it (mcts_red / mcts_black).  A sample is stored when its mover is network 0: every ply of a
+ * pairing-0 game, the red plies of a pairing-1 game (self_play.py:234).  xq_config.opponent_mode = 1 means "default pairing
+ * 1".  Slots need not be at the same ply: xq_engine_search_round2 / xq_engine_end_search2 take the evaluator outputs of
+ * BOTH networks and every slot consumes its own network's; the leaf a slot parks carries its network, row compaction
+ * numbers one row map per network (xq_engine_row_map_net: rows in slot order within each network; row_src of either
+ * network indexes the ONE set of planes the search kernel writes), leaf dedupe never shares a row between networks, and
+ * xq_engine_eval_hashnet2 evaluates every pending leaf with its network's salt.  XQ_EVAL_PRIORS output stays indexed by
+ * slot in the one priors / values array.  The evaluation cache and the root evaluation carry-over are refused by the
+ * two-network calls (self-play slots of a mixed session run without them too).  The single-network calls are unchanged:
+ * they ignore the pairing when choosing a network (the caller alternates by ply, as before) and number one row map. */
+/* pairing_host[g] for the game in slot g, now and for games xq_engine_new_games starts later (lock-step / set_roots
+ * sessions); NULL = back to the default. */
+int  xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing_host /*[G]*/);
+/* xq_engine_refill_begin with a pairing per game id (NULL: the default for every game) */
+int  xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds_host /*[total]*/, int total,
+                             const uint8_t *pairing_host /*[total], by game id, or NULL*/);
+int  xq_engine_search_round2(xq_engine *e, int round, int eval_kind0, const void *eval_a0_dev, const void *eval_v0_dev,
+                             int eval_kind1, const void *eval_a1_dev, const void *eval_v1_dev, void *planes_dev);
+int  xq_engine_end_search2(xq_engine *e, int eval_kind0, const void *eval_a0_dev, const void *eval_v0_dev,
+                           int eval_kind1, const void *eval_a1_dev, const void *eval_v1_dev);
+int  xq_engine_row_map_net(xq_engine *e, int net, const int32_t **row_src_dev, const int32_t **row_count_dev);
+/* xq_engine_read_row_history for the rows of one network (the two add up to the total) */
+int  xq_engine_read_row_history_net(xq_engine *e, int net, int32_t *rows_host, int cap, int64_t *n_rounds, int reset);
+int  xq_engine_eval_hashnet2(xq_engine *e, int salt0, int salt1);
 
 /* ---- network: fused 3x3 convolution of the residual tower (neural_network.py:54,181-187 with the
  * eval-mode BatchNorm folded into weights and bias):
