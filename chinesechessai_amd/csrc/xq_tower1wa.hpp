@@ -10,7 +10,12 @@
 // tools/gen_tower1wa.py), in which a layer's epilogue runs UNDER the next layer's first tap: the MFMAs of tap 0 issue pair
 // by pair as the accumulators they write are drained and the rows they read are stored.  Every accumulator still sees
 // (bias [+ x], tap 0: ks 0..3, tap 1: ...) in k_tower16b's order: the results are the same bits.
-// The parts outside the statement (input convolution, heads) are k_tower1w's HIP code: accumulators on literal AGPRs.
+// Which pixel a column of the 6 pixel tiles carries is a table of the generator (PIX_OF), not 16 tile + column: the pixels of
+// file 0 sit in tile 5 beside the six empty columns, rank 0 and file 8 in tile 4, and the (pixel tile, tap) pairs in which
+// every column then reads the zero padding of the 3x3 convolution - the three left taps of tile 5, the upper right tap of
+// tile 4 - are not issued in taps 1..7: 96 of a layer's 1,728 MFMAs add exact zeros and are left out, same bits.
+// The parts outside the statement (input convolution, heads) are k_tower1w's HIP code: accumulators on literal AGPRs; the
+// input convolution and the 0-block epilogue follow the same column table, the heads read LDS by pixel in plain order.
 // The lane-dependent addresses the assembly needs (54 tap addresses, store addresses, selectors, DMA source offsets) are a
 // compile-time table (g_lane_tab), 76 dwords per thread, loaded once per workgroup.
 // Reference ops: neural_network.py:54-66,181-187 with eval-mode BatchNorm folded.
@@ -133,8 +138,57 @@ static_assert(XQ_1WA_JUNK >= 4 * WBUF_BYTES + 4 * ACT_BYTES + 256 + 2 * 512 && (
 
 struct LaneTab1WA { int32_t v[256][XQ_1WA_TAB_DWORDS]; };
 
+// Which board pixel a column of a pixel tile carries (-1: none) is chosen by tools/gen_tower1wa.py (PIX_OF there): the file-0
+// pixels share tile 5 with the six empty columns, rank 0 and file 8 fill tile 4, so that whole (pixel tile, tap) pairs read
+// nothing but zero padding (XQ_1WA_DEAD_TAPS) and the body leaves their MFMAs out (XQ_1WA_SKIP_TAPS).  LDS rows stay indexed
+// by the pixel; only the addresses below, the input convolution and the 0-block epilogue know the columns.
+struct PixTab1WA { int8_t p[6][16]; };
+constexpr PixTab1WA PIX_OF_1WA = { XQ_1WA_PIX_OF };
+constexpr int DEAD_TAPS_1WA[6] = XQ_1WA_DEAD_TAPS, SKIP_TAPS_1WA[6] = XQ_1WA_SKIP_TAPS;
+// the pixel of column r16 of pixel tile NT for the HIP parts: four compile-time words of four columns each, no table in memory
+constexpr uint32_t pix_word_1wa(int nt, int j)
+{
+    uint32_t w = 0;
+    for (int c = 0; c < 4; c++) w |= (uint32_t)(uint8_t)PIX_OF_1WA.p[nt][4 * j + c] << (8 * c);
+    return w;
+}
+template <int NT> __device__ __forceinline__ int pix_of_lane_1wa(int r16)
+{
+    constexpr uint32_t w0 = pix_word_1wa(NT, 0), w1 = pix_word_1wa(NT, 1), w2 = pix_word_1wa(NT, 2), w3 = pix_word_1wa(NT, 3);
+    const int j = r16 >> 2;
+    const uint32_t w = j == 0 ? w0 : j == 1 ? w1 : j == 2 ? w2 : w3;
+    return (int)(int8_t)(w >> ((r16 & 3) * 8));
+}
+constexpr bool tap_valid_1wa(int p, int tap)
+{
+    const int y = p / 9 + tap / 3 - 1, x = p % 9 + tap % 3 - 1;
+    return p >= 0 && y >= 0 && y < 10 && x >= 0 && x < 9;
+}
+constexpr bool pix_of_1wa_ok()
+{
+    int seen[PIX] = {};
+    for (int nt = 0; nt < 6; nt++)
+        for (int c = 0; c < 16; c++) {
+            const int p = PIX_OF_1WA.p[nt][c];
+            if (p < 0 ? nt != 5 : (p >= PIX || (p & 7) != (c & 7) || seen[p]++)) return false;   // (the swizzle needs p & 7 == column & 7)
+        }
+    for (int p = 0; p < PIX; p++)
+        if (!seen[p]) return false;
+    for (int nt = 0; nt < 6; nt++) {
+        if (SKIP_TAPS_1WA[nt] & ~DEAD_TAPS_1WA[nt]) return false;
+        for (int tap = 0; tap < 9; tap++) {
+            bool any = false;
+            for (int c = 0; c < 16; c++) any = any || tap_valid_1wa(PIX_OF_1WA.p[nt][c], tap);
+            if (any == (((DEAD_TAPS_1WA[nt] >> tap) & 1) != 0)) return false;
+        }
+    }
+    return true;
+}
+static_assert(pix_of_1wa_ok(), "every pixel in one column with p & 7 == column & 7, empty columns in tile 5 only, dead taps = the all-padding ones");
+
 // the per-thread constants of the assembly body, in the register order the body loads them (tools/gen_tower1wa.py:
-// V_TA .. V_L16); formulas = k_tower1w's (tap_addr, abase, sb, lbq, sel, wsrc)
+// V_TA .. V_L16).  ta[tap][nt] + nt * 4096 (the immediate of the body's loads) = this lane's 16-byte chunk of the row of
+// pixel p + off (p = PIX_OF_1WA[nt][r16]) where the board has that neighbour, else of the zero row.
 constexpr LaneTab1WA make_lane_tab_1wa()
 {
     LaneTab1WA T{};
@@ -144,34 +198,22 @@ constexpr LaneTab1WA make_lane_tab_1wa()
         const int act_off = ACT0 + wave * ACT_BYTES;
         int32_t *o = T.v[tid];
         int k = 0;
-        const bool real5 = r16 < PIX - 80, yu0 = r16 >= 9, yd5 = r16 == 0;
-        const int Rrow = act_off + r16 * 256, r5 = r16 << 4, q4 = (((q & 1) << 3) | (q >> 1)) << 4;
+        const int r5 = r16 << 4, q4 = (((q & 1) << 3) | (q >> 1)) << 4;
         for (int tap = 0; tap < 9; tap++)
             for (int nt = 0; nt < 6; nt++) {
-                const int p = nt * 16 + r16, xx = p % 9;
-                const bool xl = xx != 0 && p < PIX, xr = xx != 8 && p < PIX;
+                const int p = PIX_OF_1WA.p[nt][r16];
                 const int dy = tap / 3 - 1, dx = tap % 3 - 1, off = dy * 9 + dx;
-                const int slot = ((r5 + off * 16) & 0x70) ^ q4;
-                const int aok = Rrow + off * 256 + slot;
-                const bool sel = dx != 0 || (nt == 0 && dy < 0) || nt == 5;
-                int a = aok;
-                if (sel) {
-                    bool ok = dx < 0 ? xl : dx > 0 ? xr : real5;
-                    if (dx == 0 && nt == 0) ok = yu0;
-                    else if (nt == 0 && dy < 0) ok = ok && yu0;
-                    if (nt == 5 && dy > 0) ok = ok && yd5;
-                    a = ok ? aok : slot + (ZROW - nt * 4096);
-                }
-                o[k++] = a;
+                const int slot = ((r5 + off * 16) & 0x70) ^ q4;              // chunk ^ ((p + off) & 7): p & 7 == r16 & 7
+                o[k++] = (tap_valid_1wa(p, tap) ? act_off + (p + off) * 256 : ZROW) + slot - nt * 4096;
             }
         const int abase = r16 * 128 + ((q ^ ((r16 >> 1) & 7)) << 4);
         o[k++] = abase;
         o[k++] = abase ^ 64;
         for (int nt = 0; nt < 6; nt++) {
-            const int p = nt * 16 + r16 < PIX ? nt * 16 + r16 : 0;
+            const int p = PIX_OF_1WA.p[nt][r16] >= 0 ? PIX_OF_1WA.p[nt][r16] : 0;
             o[k++] = act_off + p * 256 + (((((q & 1) << 3) | (q >> 1)) ^ (p & 7)) << 4);
         }
-        o[k] = 80 + r16 < PIX ? o[k - 1] : XQ_1WA_JUNK + lane * 16;      // store address of pixel tile 5
+        o[k] = PIX_OF_1WA.p[5][r16] >= 0 ? o[k - 1] : XQ_1WA_JUNK + lane * 16;      // store address of pixel tile 5
         k++;
         o[k++] = BIAS + q * 32;
         for (int sidx = 0; sidx < 2; sidx++)
@@ -193,6 +235,19 @@ constexpr LaneTab1WA make_lane_tab_1wa()
     return T;
 }
 __device__ const LaneTab1WA g_lane_tab_1wa = make_lane_tab_1wa();
+// the proof that a left-out MFMA adds zeros: in every dead (pixel tile, tap) pair every lane's address is in the zero row
+constexpr bool dead_taps_read_the_zero_row(const LaneTab1WA &T)
+{
+    constexpr int ZROW = 4 * WBUF_BYTES + 4 * ACT_BYTES;
+    for (int tid = 0; tid < 256; tid++)
+        for (int tap = 0; tap < 9; tap++)
+            for (int nt = 0; nt < 6; nt++) {
+                const int a = T.v[tid][tap * 6 + nt] + nt * 4096;
+                if (((DEAD_TAPS_1WA[nt] >> tap) & 1) && (a < ZROW || a + 16 > ZROW + 256)) return false;
+            }
+    return true;
+}
+static_assert(dead_taps_read_the_zero_row(make_lane_tab_1wa()), "a (pixel tile, tap) pair whose MFMAs are left out reads a board pixel");
 
 #define XQ_S8(b) "s" #b "0", "s" #b "1", "s" #b "2", "s" #b "3", "s" #b "4", "s" #b "5", "s" #b "6", "s" #b "7", "s" #b "8", "s" #b "9"
 #define XQ_V8(b) "v" #b "0", "v" #b "1", "v" #b "2", "v" #b "3", "v" #b "4", "v" #b "5", "v" #b "6", "v" #b "7", "v" #b "8", "v" #b "9"
@@ -272,12 +327,15 @@ __global__ __launch_bounds__(256, 1) void k_tower1wa(TowerArgs A)
     }
     barrier_dma();
     {
+        // the pixels of this lane's 6 columns (-1: none)
+        const int px[6] = { pix_of_lane_1wa<0>(r16), pix_of_lane_1wa<1>(r16), pix_of_lane_1wa<2>(r16),
+                            pix_of_lane_1wa<3>(r16), pix_of_lane_1wa<4>(r16), pix_of_lane_1wa<5>(r16) };
         uint32_t vm[2] = { 0, 0 };        // tap validity of the 6 pixels of this lane, 9 bits each
 #pragma unroll
         for (int nt = 0; nt < 6; nt++) {
-            const int o = nt * 16 + r16;
+            const int o = px[nt];
             uint32_t m = 0;
-            if (o < PIX) {
+            if (o >= 0) {
                 const int yy = o / 9, xx = o % 9;
 #pragma unroll
                 for (int t = 0; t < 9; t++) {
@@ -297,7 +355,7 @@ __global__ __launch_bounds__(256, 1) void k_tower1wa(TowerArgs A)
 #pragma unroll
             for (int nt = 0; nt < 6; nt++) {
                 const bool ok = tap_real && ((vm[nt / 3] >> ((nt % 3) * 9 + tp)) & 1u);
-                const int sp = nt * 16 + r16 + off;
+                const int sp = px[nt] + off;
                 bf[nt] = lds_ld128((ok ? pl_off + sp * 32 : ZROW + (sp & 7) * 32) + (q & 1) * 16);
             }
 #pragma unroll
@@ -337,14 +395,16 @@ __global__ __launch_bounds__(256, 1) void k_tower1wa(TowerArgs A)
         int ln;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
         const int r = ln & 15, qq = ln >> 4;
+        const int px[6] = { pix_of_lane_1wa<0>(r), pix_of_lane_1wa<1>(r), pix_of_lane_1wa<2>(r),
+                            pix_of_lane_1wa<3>(r), pix_of_lane_1wa<4>(r), pix_of_lane_1wa<5>(r) };
         int sb[6];
 #pragma unroll
         for (int nt = 0; nt < 6; nt++) {
-            const int p = nt * 16 + r < PIX ? nt * 16 + r : 0;
+            const int p = px[nt] >= 0 ? px[nt] : 0;
             sb[nt] = act_off + p * 256 + (((((qq & 1) << 3) | (qq >> 1)) ^ (p & 7)) << 4);
         }
         const int lbq = BIAS + 512 + qq * 8 * 4;
-        const bool tail_ok = r < PIX - 80;
+        const bool tail_ok = px[5] >= 0;
         using seq6 = std::make_integer_sequence<int, 6>;
         asm volatile("s_nop 15\n\ts_nop 15");                          // the last MFMAs -> v_accvgpr_read (no interlock for asm)
         epi_pair<0, false>(seq6{}, acc, sb, tail_ok, lbq, nullptr);

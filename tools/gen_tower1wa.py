@@ -16,7 +16,10 @@ that the compiler cannot interleave with.  What the assembly does that the HIP f
     can issue: group (P, K) = 12 MFMAs is ready after drain max(P, K).  Every accumulator still sees its K-steps in the
     order (tap 0: ks 0, 1, 2, 3), (tap 1: ...) - the fp32 sums are the ones k_tower16b forms, bit for bit - but the
     drain's ~100 VALU + 18 LDS instructions per pair issue in the gaps of those MFMAs;
-  * every s_waitcnt is an exact count (inserted by this script) and every hazard distance is checked.
+  * every s_waitcnt is an exact count (inserted by this script) and every hazard distance is checked;
+  * the pixels are dealt to the MFMA columns (PIX_OF below) so that four (pixel tile, tap) pairs read nothing but the zero
+    padding of the 3x3 convolution; the three of them in taps 1..7 are not issued: 1,632 of a layer's 1,728 MFMAs, same bits
+    (a left-out MFMA adds +-0 to every accumulator; the ReLU on the bf16 bits maps both zeros to 0x0000).
 
 The script is also the kernel's checker: it runs the instruction stream of a 3-block tower through a symbolic model
 (LDS rows by (layer, pair) of the data they hold, ring slots by stage, fragment registers by what was loaded into
@@ -43,6 +46,56 @@ BIAS = ZROW + 256                 # [2][128] f32
 JUNK = 159744                     # 1 KB: where lanes of pixel tile 5 that hold no pixel store (156 * 1024)
 LDS_TOTAL = JUNK + 1024
 
+# ---- pixels of the MFMA columns --------------------------------------------------------------------------------------------
+# Which board pixel (p = 9 y + x, rank y 0..9, file x 0..8) a column of a pixel tile carries is free: it lives only in the
+# lane table (make_lane_tab_1wa, xq_tower1wa.hpp); the LDS rows stay indexed by the pixel.  The columns are chosen so that
+# whole (pixel tile, tap) pairs multiply nothing but the zero padding of the 3x3 convolution:
+#   tile 5 = the 10 pixels of file 0 + the 6 columns of a 96-column wave tile that hold no pixel: no column has a left
+#            neighbour - taps 0, 3, 6 (dx = -1) read only the zero row;
+#   tile 4 = 16 of the 17 pixels of rank 0 and file 8 (all but pixel 89): no column has an upper right neighbour - tap 2;
+#   tiles 0..3 = the other 64 pixels.
+# The 32 MFMAs of a layer (8 channel tiles x 4 K-steps) of such a pair add exact zeros and are not issued (DEAD, SKIP).
+# Every pixel sits in a column with p & 7 == column & 7, as in the plain order p = 16 tile + column: the row swizzle
+# chunk ^ (p & 7) then puts the 16-lane groups of a fragment read and the 8-lane groups of a store on distinct banks.
+PAD = -1
+NPIX = 90
+
+
+def _pix_of():
+    tile5 = [9 * y for y in range(10)] + [PAD] * 6
+    edge = [p for p in range(1, 9)] + [9 * y + 8 for y in range(1, 9)]         # rank 0 (files 1..8), file 8 (ranks 1..8)
+    tile4 = [None] * 16
+    for half, pixels in ((0, edge[:8]), (8, edge[8:])):
+        for p in pixels:
+            tile4[half + (p & 7)] = p
+    taken = set(tile5) | set(tile4)
+    rest = [p for p in range(NPIX) if p not in taken]
+    tiles = [[None] * 16 for _ in range(4)]
+    seen = [0] * 8                                                             # pixels of this residue placed so far
+    for p in rest:
+        k = seen[p & 7]
+        seen[p & 7] += 1
+        tiles[k >> 1][8 * (k & 1) + (p & 7)] = p
+    return tiles + [tile4, tile5]
+
+
+def tap_valid(p, tap):
+    """does pixel p have the neighbour that tap (dy, dx) = (tap / 3 - 1, tap % 3 - 1) reads?"""
+    y, x = divmod(p, 9)
+    return p != PAD and 0 <= y + tap // 3 - 1 < 10 and 0 <= x + tap % 3 - 1 < 9
+
+
+PIX_OF = _pix_of()                                                             # [tile][column] -> pixel 0..89 | PAD
+assert all(p is not None and (p == PAD or p & 7 == c & 7) for row in PIX_OF for c, p in enumerate(row))
+DEAD = frozenset((n, tap) for n in range(6) for tap in range(9) if not any(tap_valid(p, tap) for p in PIX_OF[n]))
+# the pairs the schedule leaves out: the ones of the regular taps.  (tile 5, tap 0) runs inside the skewed first tap and is
+# issued in the committed body; XQ_1WA_SKIP_TAP0=1 ("skew" schedule only) leaves it out too (Emitter.skew: its groups shrink
+# from 12 to 10 MFMAs; where the layer has no selector MFMA - the first convolution of a block - tile 5's first MFMA, the
+# one that takes the bias row as C, is then (tap 1, ks 0) in tap_regular).  Measured: DESIGN.md section 6.
+SKIP_TAP0 = os.environ.get("XQ_1WA_SCHEDULE", "skew") == "skew" and os.environ.get("XQ_1WA_SKIP_TAP0", "0") == "1"
+SKIP = frozenset((n, tap) for (n, tap) in DEAD if 1 <= tap <= 7 or (tap == 0 and SKIP_TAP0))
+
+
 # ---- register plan ------------------------------------------------------------------------------------------------------
 # fragment pool: 30 slots of 4 VGPRs.  Main loop: buffer b (0 / 1), weight fragment m = slot 14 b + m, activation
 # fragment n = slot 14 b + 8 + n.  Skewed tap 0: activation fragment (K, n) = slot 6 K + n, weight fragments of the
@@ -53,7 +106,7 @@ def SLOT(s):
 V_TAB0 = 112                       # first register filled from the lane table (TAB_DWORDS dwords, in this order)
 V_TA = 112                         # ta[tap * 6 + nt]: activation fragment address of (tap, pixel tile), K-step 0
 V_A0, V_A1 = 166, 167              # weight fragment address, K-step parity 0 / 1
-V_SB = 168                         # sb[nt]: this lane's 16-byte chunk of pixel nt * 16 + r, channel pair 0 (pair J: ^ (J << 5))
+V_SB = 168                         # sb[nt]: this lane's 16-byte chunk of pixel PIX_OF[nt][r], channel pair 0 (pair J: ^ (J << 5))
 V_SBW5 = 174                       # store address of tile 5 (in JUNK for lanes without a pixel)
 V_LBQ = 175                        # BIAS + (lane >> 4) * 32
 V_SEL = 176                        # skip-connection selectors, two fragments
@@ -246,25 +299,31 @@ class Emitter:
         """K-steps (tap, 0..3) of the layer tagged lt (first local stage lbase) in k_tower1w's issue order: per pixel tile n
         8 MFMAs with one filler per MFMA gap - the next K-step's activation fragment of tile n, one or two of its weight
         fragments, a DMA piece.  first_load: nothing prefetched this tap's first K-step; prefetch_next: the last K-step
-        prefetches (tap + 1, 0)."""
+        prefetches (tap + 1, 0).
+        A (pixel tile, tap) pair in SKIP reads only the zero row: its MFMAs and the loads of its activation fragments are
+        left out; what rides in its slot (weight fragment loads, a DMA piece, the next tap's prefetch) moves into the free
+        gaps behind weight tiles 4..7 of the pixel tile in front of it."""
         if first_load:
             for mt in range(8):
                 self.load_a(mt, lbase + 2 * tap, 0, mt, (lt, tap, 0, mt))
             for n in range(6):
-                self.load_b(8 + n, tap, 0, n, (lt, tap, 0, n))
+                if (n, tap) not in SKIP:
+                    self.load_b(8 + n, tap, 0, n, (lt, tap, 0, n))
+        assert (0, tap) not in SKIP and not any((n, tap) in SKIP and (n + 1, tap) in SKIP for n in range(5))
         for ks in range(ks_stop):
             cur, nxt = ks & 1, (ks & 1) ^ 1
             sl, kk = ks >> 1, ks & 1
             p = 2 * tap + sl
             last = ks == 3 and not prefetch_next
-            for n in range(6):
+
+            def slot_fillers(n):
+                """what the gaps behind the first four MFMAs of pixel tile n carry, in this order"""
                 def lda(m):
                     if kk == 0:
-                        self.load_a(14 * nxt + m, lbase + p, 1, m, (lt, tap, ks + 1, m))
-                    elif ks == 1:
-                        self.load_a(14 * nxt + m, lbase + p + 1, 0, m, (lt, tap, ks + 1, m))
-                    else:
-                        self.load_a(14 * nxt + m, lbase + p + 1, 0, m, (lt, tap + 1, 0, m))
+                        return lambda: self.load_a(14 * nxt + m, lbase + p, 1, m, (lt, tap, ks + 1, m))
+                    if ks == 1:
+                        return lambda: self.load_a(14 * nxt + m, lbase + p + 1, 0, m, (lt, tap, ks + 1, m))
+                    return lambda: self.load_a(14 * nxt + m, lbase + p + 1, 0, m, (lt, tap + 1, 0, m))
                 m0 = m1 = -1
                 if kk == 0:
                     if n < 2:
@@ -278,25 +337,36 @@ class Emitter:
                         m0 = n + 2
                 if last:
                     m0 = m1 = -1
-                bslot = 14 * cur + 8 + n
-                self.mfma(TILE(0, n), 14 * cur + 0, bslot, (lt, tap, ks))
+                f = [None] * 4
                 if not last:
-                    if ks < 3:
-                        self.load_b(14 * nxt + 8 + n, tap, ks + 1, n, (lt, tap, ks + 1, n))
-                    else:
-                        self.load_b(14 * nxt + 8 + n, tap + 1, 0, n, (lt, tap + 1, 0, n))
-                self.mfma(TILE(1, n), 14 * cur + 1, bslot, (lt, tap, ks))
+                    # the next K-step's activation fragment of this pixel tile (none for a pair that is left out)
+                    if ks < 3 and (n, tap) not in SKIP:
+                        f[0] = lambda: self.load_b(14 * nxt + 8 + n, tap, ks + 1, n, (lt, tap, ks + 1, n))
+                    elif ks == 3 and (n, tap + 1) not in SKIP:
+                        f[0] = lambda: self.load_b(14 * nxt + 8 + n, tap + 1, 0, n, (lt, tap + 1, 0, n))
                 if m0 >= 0:
-                    lda(m0)
-                self.mfma(TILE(2, n), 14 * cur + 2, bslot, (lt, tap, ks))
+                    f[1] = lda(m0)
                 if m1 >= 0:
-                    lda(m1)
-                self.mfma(TILE(3, n), 14 * cur + 3, bslot, (lt, tap, ks))
+                    f[2] = lda(m1)
                 if kk == 1 and 1 <= n <= 4:
                     ls = lbase + p + 3
-                    self.dma_piece(ls, n - 1, clamp_from is not None and ls >= clamp_from)
-                for mt in range(4, 8):
-                    self.mfma(TILE(mt, n), 14 * cur + mt, bslot, (lt, tap, ks))
+                    f[3] = lambda: self.dma_piece(ls, n - 1, clamp_from is not None and ls >= clamp_from)
+                return f
+
+            for n in range(6):
+                if (n, tap) in SKIP:
+                    continue
+                f = slot_fillers(n)
+                if (n + 1, tap) in SKIP:
+                    f += [x for x in slot_fillers(n + 1) if x is not None]
+                f += [None] * (8 - len(f))
+                bslot = 14 * cur + 8 + n
+                # the tile's first MFMA of the layer where tap 0 is left out and no selector MFMA came before: C = the bias row
+                first = tap == 1 and ks == 0 and (n, 0) in SKIP and lt % 2 == 0
+                for mt in range(8):
+                    self.mfma(TILE(mt, n), 14 * cur + mt, bslot, (lt, tap, ks), first=first)
+                    if f[mt] is not None:
+                        f[mt]()
                 if kk == 1 and n == 0:
                     # B_p: stage p + 1 has landed for every wave, every wave has left stage p - 1 (its slot is refilled next)
                     self.barrier(lbase + p + 1, "B%d" % p)
@@ -438,12 +508,12 @@ class Emitter:
             lo = []
             if K not in loaded_b:
                 loaded_b.add(K)
-                lo += [("ldb", K, n) for n in range(6)]
+                lo += [("ldb", K, n) for n in range(6) if (n, 0) not in SKIP]
             lo += [("lda", P, K, o, abuf[g] + o) for o in range(2)]
             loads_of[g] = lo
             # a tile's first MFMA of the layer takes the bias row as C: the selector MFMA behind an even layer, else group (P, 0)
             mfmas_of[g] = [("mfma", TILE(2 * P + o, n), abuf[g] + o, 6 * K + n, (lt_next, 0, K), (not rx) and K == 0)
-                           for n in range(6) for o in range(2)]
+                           for n in range(6) if (n, 0) not in SKIP for o in range(2)]
 
         def emit_f(f):
             if f[0] == "ldb":
@@ -984,10 +1054,12 @@ def check_and_fill(linear, nblocks, verify=True):
     last_barrier = -1
     stores_since = {}          # bias slot read bookkeeping
     blk = 0
-    expected = {-1: [("BIAS", -1), ("INPUT",)]}
+    # expected[L, n]: the ordered terms of a tile of pixel tile n in layer L - every (tap, ks) but the taps left out for it
+    expected = {(-1, n): [("BIAS", -1), ("INPUT",)] for n in range(6)}
     for L in range(nlayers):
-        h = [("BIAS", L)] + ([("skip", L)] if L & 1 else []) + [(L, tap, ks) for tap in range(9) for ks in range(4)]
-        expected[L] = h
+        for n in range(6):
+            expected[L, n] = [("BIAS", L)] + ([("skip", L)] if L & 1 else []) + [
+                (L, tap, ks) for tap in range(9) if (n, tap) not in SKIP for ks in range(4)]
 
     def lds_retire_to(idx):
         nonlocal retired
@@ -1091,7 +1163,7 @@ def check_and_fill(linear, nblocks, verify=True):
                 if fa[1] >= retired or fb[1] >= retired:
                     fail(i, "MFMA operand not waited for (queue: %d issued, %d retired; operands %d, %d)" % (nl, retired, fa[1], fb[1]))
                 a["hist"].append(want)
-            if a["hist"] != expected[a["hist"][0][1]][:len(a["hist"])]:
+            if a["hist"] != expected[a["hist"][0][1], tile % 6][:len(a["hist"])]:
                 fail(i, "tile %d accumulates out of order: ... %s" % (tile, a["hist"][-3:]))
             if i - a["last_mfma"] < 8 and a["last_mfma"] > 0:
                 fail(i, "two MFMAs on tile %d only %d instructions apart" % (tile, i - a["last_mfma"]))
@@ -1101,8 +1173,8 @@ def check_and_fill(linear, nblocks, verify=True):
                 tile, comp = m["accread"]
                 L = m["layer"]
                 a = acc[tile]
-                if a["hist"] != expected[L]:
-                    fail(i, "tile %d read for layer %d with %d of %d terms" % (tile, L, len(a["hist"]), len(expected[L])))
+                if a["hist"] != expected[L, tile % 6]:
+                    fail(i, "tile %d read for layer %d with %d of %d terms" % (tile, L, len(a["hist"]), len(expected[L, tile % 6])))
                 if i - a["last_mfma"] < 24:
                     fail(i, "accumulator of tile %d read %d instructions behind its last MFMA" % (tile, i - a["last_mfma"]))
                 a["read"].add(comp)
@@ -1293,6 +1365,13 @@ def generate():
     consts = ("#define XQ_1WA_LDS_BYTES %d\n#define XQ_1WA_JUNK %d\n#define XQ_1WA_TAB_DWORDS %d\n#define XQ_1WA_V_LAST %d\n#define XQ_1WA_A_LAST %d\n#define XQ_1WA_S_FIRST %d\n#define XQ_1WA_S_LAST %d\n"
               % (LDS_TOTAL, JUNK, TAB_DWORDS, V_LAST, A_LAST, S_RSRC, S_LAST))
     parts.append(consts)
+    # the pixel of every MFMA column (-1: none) and, per pixel tile, the taps (bit = tap) that read only zero padding /
+    # whose MFMAs the body leaves out: the lane table is built from the first and proves the second (xq_tower1wa.hpp)
+    def mask(pairs, n):
+        return sum(1 << tap for (nn, tap) in pairs if nn == n)
+    parts.append("#define XQ_1WA_PIX_OF { %s }\n" % ", ".join("{ %s }" % ", ".join("%d" % p for p in row) for row in PIX_OF))
+    parts.append("#define XQ_1WA_DEAD_TAPS { %s }\n" % ", ".join("0x%03x" % mask(DEAD, n) for n in range(6)))
+    parts.append("#define XQ_1WA_SKIP_TAPS { %s }\n" % ", ".join("0x%03x" % mask(SKIP, n) for n in range(6)))
     return "".join(parts), allstats
 
 
