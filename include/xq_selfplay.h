@@ -72,7 +72,10 @@ int xq_device_ok(int device);
  * of class ChineseChess (chess_env.py:9) one call at a time and the parity tests in bulk.
  * ------------------------------------------------------------------------------------------ */
 
-/* ChineseChess.get_legal_moves (chess_env.py:76-121).  moves_host[n][128], counts_host[n]. */
+/* ChineseChess.get_legal_moves (chess_env.py:76-121).  moves_host[n][128], counts_host[n].
+ * The move generator (here and in the engine's search) keeps the first XQ_MAX_MOVES = 128 pseudo-legal candidates of a
+ * position, in generation order, BEFORE the suicide filter: a position with more pseudo-legal moves than that is out of
+ * contract, even when fewer than 128 of them are legal (the reference has no such limit). */
 int xq_rules_legal_moves(int n, const int8_t *boards_host, const int32_t *player_host,
                          const int32_t *red_king_host, const int32_t *black_king_host,
                          uint16_t *moves_host, int32_t *counts_host);

@@ -1,6 +1,6 @@
 """Test-side restatement of the engine's search, one evaluator shared by the engine and the oracle.
 
-TEST INFRASTRUCTURE ONLY (not a test module, not a conftest).  Three things live here:
+TEST INFRASTRUCTURE ONLY (not a test module, not a conftest).  Five things live here:
 
   peaked_eval         a deterministic "trained network" stand-in: almost all prior mass on one legal move chosen by
                       CRC-32 of the position, a small dyadic value.  Wrapped once as an oracle callback
@@ -8,16 +8,19 @@ TEST INFRASTRUCTURE ONLY (not a test module, not a conftest).  Three things live
                       engine.CallbackEvaluator), so the GPU engine and the CPU oracle read identical fp32 priors and
                       fp64 values.  Peaked priors make the search follow one line: 64 rounds reach level 63, and a
                       reused tree grows past level 64 within three plies.
+  uniform_*           all priors float32(1) / float32(n), value 0, behind the same three wrappers: every unvisited child
+                      ties, only first-index order decides (tests/test_wide_nodes_cpu.py, tests/test_gpu_wide_nodes.py).
   search_mirror       Python restatement of one MCTS.search (self_play.py:89-154) as the engine runs it: NumPy float32
                       stepwise PUCT, ordered float64 backup, one pending leaf per round of `leaf_batch` simulations - or,
                       with virtual_loss, up to `leaf_batch` pending leaves, a pending visit counting as N + 1, W - 1 on
                       every node of its path.  It starts from a given game env and a given Node: a fresh one, or the
                       subtree kept from the previous ply (the engine's opt-in tree reuse).
-  play_reuse_mirror   per ply: search, record the tree, play the argmax child, keep its subtree if it was expanded
-                      (k_play_move), otherwise start fresh.
+  play_reuse_mirror   from the start position or a given env; per ply: search, record the tree, play the argmax child,
+                      keep its subtree if it was expanded (k_play_move), otherwise start fresh.
 
 tests/test_search_mirror_cpu.py validates the mirror against the pinned oracle's search_tree before any GPU test trusts it.
 """
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -95,6 +98,43 @@ class PeakedNet:
             idx, val = peaked_eval(np.asarray(board, dtype=np.int8).reshape(90), player, len(legal))
             p = peaked_priors(len(legal), idx)
             out.append(({mv: p[j] for j, mv in enumerate(legal)}, val))
+        return out
+
+
+def uniform_priors(n_moves):
+    """all priors float32(1) / float32(n): every unvisited child ties, only first-index order decides"""
+    return np.full(n_moves, np.float32(1) / np.float32(n_moves), dtype=np.float32)
+
+
+def uniform_evaluate(board90, player, legal):
+    """search_mirror's evaluator interface for the uniform evaluator (value 0)"""
+    return list(uniform_priors(len(legal))), 0.0
+
+
+def uniform_oracle_evaluator():
+    """xo.Evaluator handing out uniform_priors and value 0"""
+    def fn(ctx, nrows, boards, players, moves, nmoves, priors, values):
+        for i in range(nrows):
+            n = int(nmoves[i])
+            p = uniform_priors(n)
+            for j in range(n):
+                priors[i * xo.MAX_MOVES + j] = p[j]
+            values[i] = 0.0
+        return 0
+    cb = xo.EVAL_FN(fn)
+    ev = xo.Evaluator(cb, None)
+    ev._keep = cb
+    return ev
+
+
+class UniformNet:
+    """predict_batch object of the uniform evaluator for engine.CallbackEvaluator"""
+
+    def predict_batch(self, rows):
+        out = []
+        for board, player, legal in rows:
+            p = uniform_priors(len(legal))
+            out.append(({mv: p[j] for j, mv in enumerate(legal)}, 0.0))
         return out
 
 
@@ -196,13 +236,18 @@ def search_mirror(game_env, root, sims, leaf_batch=8, virtual_loss=False, evalua
     return [c.mv for c in root.ch], [c.N for c in root.ch], root
 
 
-def play_reuse_mirror(sims, plies, start_moves=(), leaf_batch=8, virtual_loss=False, evaluate=peaked_evaluate, reuse=True):
-    """`plies` plies of argmax play from the start position after `start_moves`, each searched with search_mirror; with
-    `reuse` the played child's subtree is the next ply's tree if it was expanded (k_play_move), otherwise the tree is fresh.
-    Returns a list per ply of dict(flat=flatten_nodes of the tree as searched - a snapshot: a kept subtree goes on changing -,
-    root_idx, moves, counts, played)."""
+def play_reuse_mirror(sims, plies, start_moves=(), leaf_batch=8, virtual_loss=False, evaluate=peaked_evaluate, reuse=True,
+                      start_env=None):
+    """`plies` plies of argmax play from the start position after `start_moves` - or from a copy of the xo.OracleEnv
+    `start_env` (any position, e.g. one made with set_state; it is not changed) after `start_moves` -, each searched with
+    search_mirror; with `reuse` the played child's subtree is the next ply's tree if it was expanded (k_play_move),
+    otherwise the tree is fresh.  Returns a list per ply of dict(flat=flatten_nodes of the tree as searched - a snapshot:
+    a kept subtree goes on changing -, root_idx, moves, counts, played)."""
     env = xo.OracleEnv()
-    env.reset()
+    if start_env is None:
+        env.reset()
+    else:
+        C.memmove(env.p, start_env.p, C.sizeof(xo.Env))
     for m in start_moves:
         env.make_move(int(m))
     root, out, arena = Node(), [], [1]
