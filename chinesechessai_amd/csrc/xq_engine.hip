@@ -97,12 +97,16 @@ struct Eng {
     float    *priors;         // [slots][128]
     double   *values;         // [slots]
     // evaluation cache (xq_engine_set_eval_cache): the evaluator's answer - legal-move priors and value - for a position
-    // (board + side to move = everything the network reads, neural_network.py:128-146) is kept for two plies and handed to
-    // any later leaf that is the same position: no network row.  ec_state[i] = epoch << 32 | launch that filled the entry
-    // (0xffffffff: reserved, being filled); ec_key[i] = 12 board dwords, side + 2, n, value bits, 0; ec_prior[i][128].
+    // (board + side to move = everything the network reads, neural_network.py:128-146) is kept for ec_keep plies and handed
+    // to any later leaf that is the same position waiting for the same network: no network row.  ec_state[i] = epoch << 32 |
+    // launch that filled the entry (0xffffffff: reserved, being filled); ec_key[i] = 12 board dwords, side + 2 + 4 * network,
+    // n, value bits, 0; ec_prior[i][128].
     // leaf_ec[slot]: -1 nothing, >= 0 the entry this pending leaf reads, <= -2 the entry -(i + 2) it fills when consumed
+    // ec_keep: plies an entry lives, 2 (one network moves every ply) unless xq_engine_set_per_slot_reuse asked for 3 (in a
+    // game of two networks each searches every second ply: what it evaluated at ply p is wanted again at ply p + 2)
     int ec_on, ec_mask;
     unsigned ec_epoch, ec_seq;
+    int ec_keep;
     unsigned long long *ec_state;
     uint32_t *ec_key;
     float    *ec_prior;
@@ -144,7 +148,7 @@ struct Eng {
 struct EvalOut { const void *a; const void *v; int kind; int pad; };
 struct EvalPair { EvalOut o[2]; };
 
-__device__ __forceinline__ void eval_cache_fill(const Eng &E, int i, uint32_t board_dword, int side, int n, float p0, float p1, float value);
+__device__ __forceinline__ void eval_cache_fill(const Eng &E, int i, uint32_t board_dword, int side, int net, int n, float p0, float p1, float value);
 // (accessors of the evaluation cache: past the L2s - see eval_cache_fill)
 __device__ __forceinline__ uint32_t ec_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ec_st(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -456,7 +460,7 @@ __device__ void consume_eval(const Eng &E, int g, int slot, WaveLds &L, const Tr
         for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
         p0 = e0 / sum; p1 = e1 / sum;
         if (ec <= -2) {
-            eval_cache_fill(E, -ec - 2, lane < 12 ? E.leaf_board[(size_t)slot * 12 + lane] : 0u, E.leaf_side[slot], n, p0, p1, (float)v);
+            eval_cache_fill(E, -ec - 2, lane < 12 ? E.leaf_board[(size_t)slot * 12 + lane] : 0u, E.leaf_side[slot], lnet, n, p0, p1, (float)v);
             if (lane == 0) E.ec_stats[E.ec_stat_stride + slot] += 1u;
         } else if (ec >= 0) {                                 // verify mode
             const float *pr = E.ec_prior + (size_t)ec * MAXM;
@@ -612,12 +616,14 @@ __device__ __forceinline__ uint64_t position_hash(uint32_t my_dword, int side, i
 
 // Evaluation cache, fill side: the wave that consumes a leaf whose probe reserved entry i writes the position, its priors
 // (before any root noise) and its value, then the state word.  Readers accept the entry from the next launch on.
-__device__ __forceinline__ void eval_cache_fill(const Eng &E, int i, uint32_t board_dword /* lane < 12 */, int side, int n,
+// (the key carries the network whose answer this is: one table serves both networks of a two-network round; a
+// single-network launch has net == 0 and stores the bits it always stored)
+__device__ __forceinline__ void eval_cache_fill(const Eng &E, int i, uint32_t board_dword /* lane < 12 */, int side, int net, int n,
                                                 float p0, float p1, float value)
 {
     const int lane = XQ_LANE;
     uint32_t k = board_dword;
-    if (lane == 12) k = (uint32_t)(side + 2);
+    if (lane == 12) k = (uint32_t)(side + 2 + 4 * net);
     else if (lane == 13) k = (uint32_t)n;
     else if (lane == 14) k = __float_as_uint(value);
     else if (lane == 15) k = 0u;
@@ -656,8 +662,9 @@ __device__ __forceinline__ DedupeLook dedupe_prepare(const Eng &E, int slot, uin
 // Evaluation cache, look-up side (called for a leaf about to wait for the network).  Returns the entry that holds this
 // position's evaluation (>= 0: no network row needed), or -(i + 2) after reserving entry i for it (the wave that consumes
 // the leaf fills it), or -1 (no luck: evaluated, not kept).  An entry is read only if it was filled in an EARLIER launch -
-// kernel boundaries make it visible, nothing inside a launch has to - and within the last two plies (the epoch): older
-// entries are free to be taken over, so the table needs no clearing and stays as small as two plies of evaluations.
+// kernel boundaries make it visible, nothing inside a launch has to - and within the last ec_keep plies (the epoch): older
+// entries are free to be taken over, so the table needs no clearing and stays as small as that many plies of evaluations.
+// `net`: the network the leaf waits for - part of the compared key, as it is part of the hash.
 //
 // `first` / `have_first`: the state word of the first entry, loaded by the caller ahead of time (the search kernel sends the
 // look on its way before the move generation: one of the probe's two memory round trips is then hidden).
@@ -668,17 +675,17 @@ __device__ __forceinline__ unsigned eval_cache_pos(const Eng &E, uint64_t h) { r
 // this very position, put there by a wave whose own probe has just reserved the cache entry (in the opening thousands of
 // waves arrive with one position).  Such a leaf still takes an answer the cache HAS, but does not join the race for an
 // entry that is free: 16,384 compare-and-swaps on one word cost more than the cache saves.
-__device__ __forceinline__ int eval_cache_probe(const Eng &E, uint64_t h, uint32_t my_dword, int side,
+__device__ __forceinline__ int eval_cache_probe(const Eng &E, uint64_t h, uint32_t my_dword, int side, int net,
                                                 unsigned long long first = 0ull, bool have_first = false, bool crowded = false)
 {
     const int lane = XQ_LANE;
-    const unsigned mask = (unsigned)E.ec_mask, epoch = E.ec_epoch, seq = E.ec_seq;
+    const unsigned mask = (unsigned)E.ec_mask, epoch = E.ec_epoch, seq = E.ec_seq, too_old = (unsigned)E.ec_keep - 1u;
     unsigned pos = eval_cache_pos(E, h);
     for (int probe = 0; probe < 4; probe++, pos = (pos + 1) & mask) {
         const unsigned long long raw = (probe == 0 && have_first) ? first : ec_ld64(&E.ec_state[pos]);
         const unsigned long long st = uni64(raw);
         const unsigned ep = (unsigned)(st >> 32), filled = (unsigned)st;
-        if (epoch - ep > 1u) {                                  // older than the ply before this one (or never used): take it
+        if (epoch - ep > too_old) {                             // older than the plies an entry is kept (or never used): take it
             if (crowded) return -1;
             unsigned long long old = 0;
             if (lane == 0) old = atomicCAS(&E.ec_state[pos], st, ((unsigned long long)epoch << 32) | 0xffffffffull);
@@ -687,7 +694,7 @@ __device__ __forceinline__ int eval_cache_probe(const Eng &E, uint64_t h, uint32
         }
         if (filled >= seq) return -1;                           // reserved or filled in this launch: contents not visible yet
         const uint32_t theirs = lane < 13 ? ec_old(&E.ec_key[(size_t)pos * 16 + lane]) : 0u;
-        const uint32_t mine = lane < 12 ? my_dword : (uint32_t)(side + 2);
+        const uint32_t mine = lane < 12 ? my_dword : (uint32_t)(side + 2 + 4 * net);
         if (__ballot(lane < 13 && theirs != mine) == 0ull) {
             return (int)pos;
         }
@@ -769,7 +776,7 @@ __device__ __forceinline__ void record_leaf(const Eng &E, int slot, WaveLds &L, 
     if (E.dedupe) look = dedupe_prepare(E, slot, my_dword, side, h, net);   // (board + side past the L2s, first look at the table)
     int ec = -1;
     if (E.ec_on) {
-        ec = eval_cache_probe(E, h, my_dword, side, 0ull, false, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
+        ec = eval_cache_probe(E, h, my_dword, side, net, 0ull, false, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
         if (lane == 0) E.leaf_ec[slot] = ec;
     }
     // (last: the planes' stores travel while it waits for the table; a leaf the cache answers needs no row at all)
@@ -1143,7 +1150,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
             for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
             p0 = e0 / sum; p1 = e1 / sum;
             if (p_ec <= -2) {
-                eval_cache_fill(E, -p_ec - 2, lbw, lside, n, p0, p1, (float)v);
+                eval_cache_fill(E, -p_ec - 2, lbw, lside, cnet, n, p0, p1, (float)v);    // (a ply's whole tree has one network)
                 if (lane == 0) E.ec_stats[E.ec_stat_stride + slot] += 1u;
             } else if (p_ec >= 0) {
                 // verify mode (ec_on == 2): the leaf was evaluated although the cache holds its position - they must agree
@@ -1326,7 +1333,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
                 const uint32_t bdw = lane < 12 ? pack_dword(L.bd, lane) : 0u;
                 int ec = -1;
                 if (E.ec_on) {
-                    ec = eval_cache_probe(E, h, bdw, leaf_side, ec_first, true, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
+                    ec = eval_cache_probe(E, h, bdw, leaf_side, net, ec_first, true, E.dedupe && (unsigned)(look.ent >> 32) == E.dd_tag);
                     if (lane == 0) E.leaf_ec[slot] = ec;
                 }
                 if (E.dedupe && (ec < 0 || E.ec_on == 2)) dedupe_finish(E, slot, bdw, leaf_side, look, net);
@@ -1579,7 +1586,8 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
     wave_sync();
 
     // sample record (self_play.py:234-239)
-    const bool store = (gs.side == 1) || E.pairing[g] == 0;          // the mover is network 0 (pairing 1: red plies only, self_play.py:234)
+    const int pair_v = uni((int)E.pairing[g]);
+    const bool store = (gs.side == 1) || pair_v == 0;                // the mover is network 0 (pairing 1: red plies only, self_play.py:234)
     if (store) {
         const size_t si = (size_t)g * XQ_MAX_PLIES + gs.n_samples;
         if (lane < 12) E.s_board[si * 12 + lane] = E.board[(size_t)g * 12 + lane];
@@ -1658,13 +1666,15 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
         // row for exactly this (board, player).  The evaluator is deterministic and row-independent, so that
         // second evaluation returns the same priors bit for bit: take them from the child's expansion and leave
         // the tree as round 0 would (root.visit_count = first batch size, children unvisited, self_play.py:103-148).
+        // The priors are those of the network that searched this ply; the next root is searched by the same network
+        // exactly when the slot's pairing is 0, so a pairing-1 slot evaluates its root afresh (xq_engine_set_per_slot_reuse).
         const int c = first + pick, n = T.nc[c], fc = T.first[c];
         const int j0 = lane, j1 = lane + 64;
         const uint16_t m0 = j0 < n ? T.mv[fc + j0] : (uint16_t)0, m1 = j1 < n ? T.mv[fc + j1] : (uint16_t)0;
         const float p0 = j0 < n ? T.P[fc + j0] : 0.f, p1 = j1 < n ? T.P[fc + j1] : 0.f;
         // (the child's move list is the legal-move list the leaf's make_move produced: it must equal this one)
         const bool same = (j0 >= n || m0 == L.legal[j0]) && (j1 >= n || m1 == L.legal[j1]);
-        const bool ok = n != 0 && n == mr.n_legal && __all(same);
+        const bool ok = n != 0 && n == mr.n_legal && __all(same) && pair_v == 0;
         wave_sync();
         if (ok) {
             if (j0 < n) { const int x = 1 + j0; T.N[x] = 0; T.W[x] = 0.0; T.P[x] = p0; T.mv[x] = m0; T.first[x] = 0; T.nc[x] = 0; T.fl[x] = 0; }
@@ -2133,7 +2143,8 @@ struct xq_engine {
     unsigned row_seq = 0;                     // search rounds launched with row compaction (index into row_hist)
     bool row_map_fetched = false;             // xq_engine_row_map since row compaction was last switched: the evaluator knows the layout
     unsigned dd_tag = 0;                      // round tag of the leaf dedupe table (never 0: the cleared table's tag)
-    unsigned ec_epoch = 16, ec_seq = 0;       // evaluation cache: ply counter (+2 at every new set of roots), launch counter
+    unsigned ec_epoch = 16, ec_seq = 0;       // evaluation cache: ply counter (+E.ec_keep at every new set of roots), launch counter
+    int slot_reuse = 0;                       // xq_engine_set_per_slot_reuse: two-network rounds may use the cache and the carry-over
     // The cache's key is the position (board + side), its payload the priors BY INDEX into the leaf's legal-move list - and
     // that list also depends on the two king caches.  Play from roots whose caches say where the kings stand keeps them so
     // (wave_make_move updates them on every king move and capture), so there the position fixes the list.  Roots handed to
@@ -2151,6 +2162,8 @@ struct xq_engine {
 };
 
 static void eval_cache_apply(xq_engine *e) { e->E.ec_on = e->ec_roots_ok ? e->ec_want : 0; }
+// a new set of roots, possibly new weights: every entry falls out of the window of E.ec_keep plies
+static void eval_cache_age_out(xq_engine *e) { e->ec_epoch += (unsigned)e->E.ec_keep; }
 
 // both king caches of a caller's root name the square where that king stands (a missing king: NO_KING)
 static bool king_caches_true(const int8_t *board, int rk, int bk)
@@ -2206,6 +2219,7 @@ extern "C" int xq_engine_create(const xq_config *cfg, xq_engine **out)
     E.want_check = nrounds >= 12 ? 1 : 0;       // check_history only matters once 12 plies fit a path
     E.temperature = cfg->temperature;
     E.leaf_slots = 1;
+    E.ec_keep = 2;
     const size_t G = (size_t)E.G, NC = (size_t)E.ncap;
     int bad = 0;
     bad |= dalloc(e, E.board, G * 12); bad |= dalloc(e, E.gs, G); bad |= dalloc(e, E.pos_hist, G * PATH_CAP);
@@ -2345,7 +2359,7 @@ extern "C" int xq_engine_new_games(xq_engine *e, const uint32_t *seeds)
     HIPCHK(hipMemcpyAsync(e->E.uniforms, u.data(), u.size() * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));          // u is a local: copy must finish
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));
-    e->ec_epoch += 2;                                                    // new games, possibly new weights: nothing cached survives
+    eval_cache_age_out(e);                                               // new games, possibly new weights: nothing cached survives
     e->ec_roots_ok = true;                                               // (the start position: true king caches)
     eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
@@ -2517,7 +2531,7 @@ extern "C" int xq_engine_set_roots(xq_engine *e, const int8_t *boards, const int
     HIPCHK(hipMemcpyAsync(e->stage_state, state, G * XQ_STATE_WORDS * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));     // k_set_roots counts them
-    e->ec_epoch += 2;
+    eval_cache_age_out(e);
     e->ec_roots_ok = true;
     for (size_t g = 0; g < G && e->ec_roots_ok; g++)
         e->ec_roots_ok = king_caches_true(boards + g * 90, state[g * XQ_STATE_WORDS + XQ_S_RED_KING], state[g * XQ_STATE_WORDS + XQ_S_BLACK_KING]);
@@ -2578,9 +2592,11 @@ extern "C" int xq_engine_set_search_stamps(void *dev_u64x16_per_game)
 }
 
 // a two-network round needs what a second network always needed: no evaluation cache (its key is the position alone) and
-// no root evaluation carry-over (the carried priors are the mover's network's)
+// no root evaluation carry-over (the carried priors are the mover's network's) - unless xq_engine_set_per_slot_reuse
+// put the network into the cache's key and the pairing into the carry-over's condition
 static int two_net_ok(xq_engine *e)
 {
+    if (e->slot_reuse) return 0;
     if (e->E.ec_on || e->ec_want) return fail(XQ_E_INVALID, "a two-network round cannot use the evaluation cache (two networks answer differently for one position): xq_engine_set_eval_cache(e, 0)");
     if (e->E.eval_carry) return fail(XQ_E_INVALID, "a two-network round cannot use the root evaluation carry-over (the carried priors are the mover's network's)");
     return 0;
@@ -2719,7 +2735,7 @@ extern "C" int xq_engine_set_eval_cache(xq_engine *e, int log2_entries)
         HIPCHK(hipMemsetAsync(e->E.leaf_ec, 0xff, (size_t)e->E.G * 64 * 4, e->stream));
         e->E.ec_mask = (int)(n - 1);
     }
-    e->ec_epoch += 2;
+    eval_cache_age_out(e);
     e->ec_want = verify ? 2 : 1;
     eval_cache_apply(e);                           // (off all the same while the games' roots carry stale king caches: xq_engine::ec_want)
     e->E.ec_stat_stride = e->E.G * 64;
@@ -2853,7 +2869,7 @@ extern "C" int xq_engine_play_move(xq_engine *e)
         if (ev) HIPCHK(hipEventRecord(ev->first, e->stream));
     }
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));
-    e->ec_epoch += 1;                                                    // the evaluation cache keeps two plies
+    e->ec_epoch += 1;                                                    // the evaluation cache keeps E.ec_keep plies
     hipLaunchKernelGGL(k_play_move, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());
     if (ev) HIPCHK(hipEventRecord(ev->second, e->stream));
@@ -2882,6 +2898,22 @@ extern "C" int xq_engine_set_root_eval_carry(xq_engine *e, int enable)
         if (dalloc(e, E.root_ready, (size_t)E.G) || dalloc(e, E.roots_not_ready, (size_t)1)) return fail(XQ_E_HIP, "hipMalloc failed");
     }
     E.eval_carry = enable ? 1 : 0;
+    return 0;
+}
+
+// Opt-in (default off): the two work eliminations above in two-network rounds and sessions.  The carry-over becomes a
+// per-slot decision - the played child's priors are the network's that searched this ply, and the same network searches
+// the next root exactly when the slot's pairing is 0 (k_play_move) - and the cache's compared key carries the leaf's
+// network, so one table serves both.  keep_plies = the cache's window: 2 as in single-network play, 3 when pairing-1
+// games are played - there each network searches every second ply, so what it evaluated at ply p (the root of ply p + 2
+// among it, which no carry-over provides) is wanted again at ply p + 2.  Every cached entry is aged out by the call.
+extern "C" int xq_engine_set_per_slot_reuse(xq_engine *e, int enable, int keep_plies)
+{
+    if (!e) return fail(XQ_E_INVALID, "null engine");
+    if (keep_plies != 2 && keep_plies != 3) return fail(XQ_E_INVALID, "per-slot reuse: keep_plies must be 2 or 3");
+    e->ec_epoch += 3;                                                    // (past the wider of the two windows)
+    e->slot_reuse = enable ? 1 : 0;
+    e->E.ec_keep = enable ? keep_plies : 2;
     return 0;
 }
 
@@ -2917,8 +2949,9 @@ extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int 
             if (pairing[i] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
             second |= pairing[i] != 0;
         }
-    if (second && (e->E.eval_carry || e->ec_want))
-        return fail(XQ_E_INVALID, "a refill session with a second network cannot use the evaluation cache or the root evaluation carry-over");
+    if (second && !e->slot_reuse && (e->E.eval_carry || e->ec_want))
+        return fail(XQ_E_INVALID, "a refill session with a second network cannot use the evaluation cache or the root evaluation carry-over "
+                                  "(xq_engine_set_per_slot_reuse allows both)");
     HIPCHK(hipSetDevice(e->cfg.device));
     const size_t G = (size_t)e->E.G, T = (size_t)total;
     if (total > e->refill_cap) {             // (buffers of an earlier, smaller session stay in e->allocs until destroy)
@@ -2943,7 +2976,7 @@ extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int 
     HIPCHK(hipMemsetAsync(e->out_gs, 0, T * sizeof(GameS), e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));          // locals: the copies must finish
     if (e->E.eval_carry) HIPCHK(hipMemsetAsync(e->E.roots_not_ready, 0, 4, e->stream));
-    e->ec_epoch += 2;                                                    // new games, possibly new weights: nothing cached survives
+    eval_cache_age_out(e);                                               // new games, possibly new weights: nothing cached survives
     e->ec_roots_ok = true;                                               // (the start position: true king caches)
     eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
@@ -2974,8 +3007,9 @@ extern "C" int xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing)
             if (pairing[g] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
             second |= pairing[g] != 0;
         }
-    if (second && (e->E.eval_carry || e->ec_want))
-        return fail(XQ_E_INVALID, "a second network cannot be combined with the evaluation cache or the root evaluation carry-over");
+    if (second && !e->slot_reuse && (e->E.eval_carry || e->ec_want))
+        return fail(XQ_E_INVALID, "a second network cannot be combined with the evaluation cache or the root evaluation carry-over "
+                                  "(xq_engine_set_per_slot_reuse allows both)");
     HIPCHK(hipSetDevice(e->cfg.device));
     if (pairing) HIPCHK(hipMemcpyAsync(e->pairing_init, pairing, G, hipMemcpyHostToDevice, e->stream));
     else HIPCHK(hipMemsetAsync(e->pairing_init, e->E.opponent_mode ? 1 : 0, G, e->stream));

@@ -27,6 +27,23 @@ def check_per_slot_evaluators(evaluator, opponent_evaluator):
                                "carry the leaf's network): use HashNetEvaluator / TorchNetEvaluator, or the lock-step play()")
 
 
+def check_reuse_evaluators(evaluator, opponent_evaluator):
+    """`reuse=True` of a two-network session vouches for evaluators whose answer depends on the position only; a
+    CallbackEvaluator makes no such promise (and cannot take part in a per-slot session anyway).  Raised before any
+    device call."""
+    for ev in (evaluator, opponent_evaluator):
+        if isinstance(ev, CallbackEvaluator):
+            raise _lib.XqError("reuse=True (evaluation cache and root carry-over in a two-network session) cannot be combined "
+                               "with a CallbackEvaluator: its network may answer differently for one position")
+
+
+def check_keep_plies(keep_plies):
+    """The evaluation cache's window of a per-slot reuse session: 2 or 3 plies (ValueError before any device call)."""
+    if isinstance(keep_plies, bool) or keep_plies not in (2, 3):
+        raise ValueError("keep_plies must be 2 or 3, got %r" % (keep_plies,))
+    return int(keep_plies)
+
+
 def normalise_pairing(pairing, total, has_opponent):
     """The pairing array of `total` games as uint8 (None: all 1 with an opponent, else None = the engine's default).
     Raises ValueError for a wrong length, a value other than 0 / 1, or a pairing-1 game without an opponent."""
@@ -156,11 +173,15 @@ class TorchNetEvaluator:
     def bind(self, engine, net=0, planes_of=None):
         """net = 1: bound as network 1 of a per-slot session (SelfPlayEngine.search(..., per_slot=True)): rows by
         row_map_net(1), own logits / values, and the input planes the search kernel wrote into `planes_of`'s storage -
-        network 0's - which are written once (without `planes_of`, e.g. beside a HashNetEvaluator, it owns them)."""
+        network 0's - which are written once (without `planes_of`, e.g. beside a HashNetEvaluator, it owns them).  The
+        evaluation cache is the engine's, one table for both networks: network 0's evaluator governs it (size, verify
+        mode, statistics, suspension), network 1's leaves its settings alone."""
         torch = self.torch
+        self._bound_net = net
         engine.set_row_compaction(self.row_compaction)
         if self.row_compaction:
             engine.set_leaf_dedupe(self.leaf_dedupe)
+        if self.row_compaction and not net:
             use = self.eval_cache and self.eval_cache_suspended == 0
             engine.set_eval_cache(use, verify=self.eval_cache_verify)
             if use:
@@ -186,8 +207,10 @@ class TorchNetEvaluator:
         return self.storage.data_ptr()
 
     def after_play(self, engine):
-        """called by SelfPlayEngine.play / play_refill when the games are over: the evaluation cache's self-assessment"""
-        if not self.eval_cache:
+        """called by SelfPlayEngine.play / play_refill when the games are over: the evaluation cache's self-assessment
+        (network 0's evaluator alone: the rows it weighs the hits against are those of both networks - row_history() is
+        the sum of row_history_net(0) and row_history_net(1))"""
+        if not self.eval_cache or getattr(self, "_bound_net", 0):
             return
         if engine.eval_cache:
             hits, fills, _ = engine.eval_cache_stats()
@@ -278,6 +301,8 @@ class SelfPlayEngine:
         self.row_compaction = False
         self.leaf_dedupe = False
         self.eval_cache = False
+        self._slot_reuse = False                                # set_per_slot_reuse: cache and carry-over in two-network sessions
+        self.reuse_keep_plies = None                            # play_refill(reuse=True): None = 3 when a game has pairing 1, else 2
         self._noise = self._vloss = False
         self.tree_reuse = False
         if stream is not None:
@@ -331,17 +356,31 @@ class SelfPlayEngine:
         _lib.check(self.L.xq_engine_set_root_eval_carry(self.h, 1 if enable else 0))
         self.root_eval_carry = self._carry_on = bool(enable)
 
-    def _auto_carry(self, evaluator, opponent_evaluator):
-        """Decide the carry-over for the games about to start (play / play_refill)."""
+    def set_per_slot_reuse(self, enable=True, keep_plies=3):
+        """The root evaluation carry-over and the evaluation cache in two-network sessions (xq_engine_set_per_slot_reuse;
+        off by default: such sessions then refuse both).  The carry-over is decided per slot - a pairing-0 slot carries
+        its root as in single-network play, a pairing-1 slot evaluates it afresh with the other network - and the
+        cache's key carries the leaf's network.  keep_plies: the cache's window, 2 or 3 plies; sessions with pairing-1
+        games want 3, because there each network searches every second ply and meets its own evaluations two plies
+        later.  play_refill(reuse=True) calls this by itself.  Call before set_pairing / new games."""
+        keep_plies = check_keep_plies(keep_plies)
+        _lib.check(self.L.xq_engine_set_per_slot_reuse(self.h, 1 if enable else 0, keep_plies))
+        self._slot_reuse = bool(enable)
+
+    def _auto_carry(self, evaluator, opponent_evaluator, reuse=False):
+        """Decide the carry-over for the games about to start (play / play_refill).  reuse: a per-slot session with
+        set_per_slot_reuse on - the second network no longer rules the carry-over out, the rule is otherwise the same."""
         if self.root_eval_carry is not None:
-            if self.root_eval_carry and opponent_evaluator is not None:
+            if self.root_eval_carry and opponent_evaluator is not None and not reuse:
                 raise _lib.XqError("root evaluation carry-over needs one network for both sides (the carried priors are the mover's network's)")
             return self._carry_on
         # automatic only where a carried root costs nothing by itself: with row compaction it simply has no row in round
         # 0.  Without compaction skipping round 0 takes a blocking read of roots_not_ready every ply (the host would stop
         # running ahead of the GPU), which nobody asked for: those evaluators get the carry-over by set_root_eval_carry(True)
+        second_ok = opponent_evaluator is None or bool(
+            reuse and getattr(opponent_evaluator, "deterministic", False) and getattr(opponent_evaluator, "row_compaction", False))
         want = bool(getattr(evaluator, "deterministic", False) and getattr(evaluator, "row_compaction", False)
-                    and opponent_evaluator is None and not self.opponent_mode
+                    and second_ok and not self.opponent_mode
                     and not self._noise and not self._vloss and not self.tree_reuse)
         if want != self._carry_on:
             _lib.check(self.L.xq_engine_set_root_eval_carry(self.h, 1 if want else 0))
@@ -461,7 +500,9 @@ class SelfPlayEngine:
         searched with the network of the side to move at its root - `evaluator` (network 0) unless the game's pairing is 1
         and black is to move, then `opponent_evaluator` (network 1).  Each round runs the tree kernel, then BOTH evaluators,
         each on the rows of its own network.  The evaluation cache and the root evaluation carry-over are off in such a
-        session, for its self-play slots too.  Both evaluators must have been bound (play_refill does; else _bind(ev0, ev1,
+        session, for its self-play slots too, unless set_per_slot_reuse switched them on: then a carried root (pairing-0
+        slots only) has no row in round 0 with row compaction, and without it round 0 is launched and ready roots
+        return at once.  Both evaluators must have been bound (play_refill does; else _bind(ev0, ev1,
         per_slot=True))."""
         if per_slot:
             if opponent_evaluator is None:
@@ -607,8 +648,9 @@ class SelfPlayEngine:
                     ev.bind(self, net=1, planes_of=evaluator if isinstance(evaluator, TorchNetEvaluator) else None)
                 else:
                     ev.bind(self)
-        if opponent_evaluator is not None:
-            self.set_eval_cache(False)        # two networks answer differently for one position
+        if opponent_evaluator is not None and not (per_slot and self._slot_reuse):
+            self.set_eval_cache(False)        # two networks answer differently for one position (the key of a
+                                              # set_per_slot_reuse session carries the network: there the cache stays)
 
     def play(self, evaluator, seeds, opponent_evaluator=None, uniforms=None, check_every=8, read=True,
              temperature_schedule=None):
@@ -646,7 +688,7 @@ class SelfPlayEngine:
         return self.read_results() if read else None
 
     def play_refill(self, evaluator, seeds, records_ptr, check_every=4, max_plies=None, on_ply=None,
-                    opponent_evaluator=None, pairing=None):
+                    opponent_evaluator=None, pairing=None, reuse=False):
         """`len(seeds)` games through the engine's G slots with refill (xq_engine_refill_*): a finished game's
         slot restarts on the next unplayed seed at once, like the reference's pool (self_play.py:404-408).
         `records_ptr`: device buffer of len(seeds) * 70 sample records (distributed.RECORD_BYTES each), filled
@@ -656,16 +698,24 @@ class SelfPlayEngine:
         opponent black, red plies stored only - self_play.py:190-198, 211, 234; default all 1): the reference trainer's
         two halves of an epoch (trainer.py:186-209) in ONE session - the mover's network is chosen per slot on the device
         (search(per_slot=True)), so slots may be at any ply.  Such a session runs without the evaluation cache and the
-        root evaluation carry-over, its self-play slots included."""
+        root evaluation carry-over, its self-play slots included - unless `reuse=True` (set_per_slot_reuse): then
+        pairing-0 slots carry their roots, the cache serves both networks (its key carries the network; network 0's
+        evaluator governs it) and its window is 3 plies when any game has pairing 1, else 2 (`reuse_keep_plies` on the
+        engine overrides the choice).  Without an opponent `reuse` changes nothing."""
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         total = len(seeds)
         two = opponent_evaluator is not None
         pairing = normalise_pairing(pairing, total, two)
         if two:
+            if reuse:
+                check_reuse_evaluators(evaluator, opponent_evaluator)
             check_per_slot_evaluators(evaluator, opponent_evaluator)
         elif self.opponent_mode:
             raise _lib.XqError("play_refill on an opponent-mode engine needs opponent_evaluator")
-        carry = self._auto_carry(evaluator, opponent_evaluator)
+        reuse = bool(reuse and two)
+        if reuse or self._slot_reuse:        # (a session that never asked for it makes no call)
+            self.set_per_slot_reuse(reuse, keep_plies=(self.reuse_keep_plies or (3 if pairing.any() else 2)) if reuse else 2)
+        carry = self._auto_carry(evaluator, opponent_evaluator, reuse=reuse)
         self._bind(evaluator, opponent_evaluator, per_slot=two)
         _lib.check(self.L.xq_engine_refill_begin2(self.h, _lib.ptr(seeds), total, _lib.ptr(pairing)))
         active = np.zeros(1, np.int32)
@@ -677,7 +727,8 @@ class SelfPlayEngine:
             _lib.check(self.L.xq_engine_play_move(self.h))
             poll = plies % check_every == check_every - 1
             _lib.check(self.L.xq_engine_refill_step(self.h, C.c_void_p(records_ptr), _lib.ptr(active) if poll else None))
-            skip0 = carry and not self.row_compaction and self.roots_not_ready() == 0   # (after the refill: restarted slots need their round 0)
+            # (after the refill: restarted slots need their round 0; a per-slot search launches round 0 anyway)
+            skip0 = carry and not two and not self.row_compaction and self.roots_not_ready() == 0
             if on_ply is not None:
                 on_ply(plies)
             plies += 1

@@ -14,7 +14,7 @@ from . import _lib
 from .chess_env import ChineseChess, decode_move, format_end_reason, _sq
 from .config import MAX_MOVES, MCTS_SIMULATIONS
 from .engine import (CallbackEvaluator, HashNetEvaluator, SelfPlayEngine, TorchNetEvaluator, check_per_slot_evaluators,
-                     normalise_pairing)
+                     check_reuse_evaluators, normalise_pairing)
 
 
 class InterruptedWithResults(Exception):
@@ -253,14 +253,17 @@ def epoch_pairing(num_games, has_opponent):
 
 
 def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, opponent_network=None, slots=None,
-                    seeds=None):
+                    seeds=None, reuse=False):
     """The self-play of one trainer epoch (trainer.py:186-209: parallel_self_play(model, num_games // 2) and then
     parallel_self_play(model, num_games - num_games // 2, opponent_network=old_model)) in ONE refill session: both
     kinds of game go through the same `slots` concurrent slots and a finished game's slot takes the next game at once,
     whichever kind (self_play.py:404-408).  Game ids below num_games // 2 are self-play, the rest are `network` red vs
     `opponent_network` black and hold red plies only (self_play.py:234); without an opponent every game is self-play.
     Returns [(game_data, winner, end_reason)] in game-id order, each entry what parallel_self_play returns for that
-    game's seed (failed games are dropped as there).  `seeds`: one per game (default: drawn from np.random)."""
+    game's seed (failed games are dropped as there).  `seeds`: one per game (default: drawn from np.random).
+    `reuse=True`: the session keeps the root evaluation carry-over (its self-play slots) and the evaluation cache (both
+    networks, three-ply window) that a two-network session otherwise gives up (SelfPlayEngine.set_per_slot_reuse);
+    results are the same.  Without an opponent it changes nothing."""
     num_games = int(num_games)
     if num_games < 1:
         raise ValueError("self_play_epoch: num_games must be at least 1")
@@ -278,6 +281,8 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
     ev = _evaluator_for(network)
     ev_b = _evaluator_for(opponent_network) if two else None
     if two:
+        if reuse:
+            check_reuse_evaluators(ev, ev_b)
         check_per_slot_evaluators(ev, ev_b)
         if getattr(ev_b, "planes_format", 0) != getattr(ev, "planes_format", 0):
             raise ValueError("both networks must use the same planes format")
@@ -289,7 +294,8 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
                          planes_format=getattr(ev, "planes_format", _lib.PLANES_NONE))
     try:
         records = torch.zeros(num_games * _lib.MAX_PLIES * RECORD_BYTES, dtype=torch.uint8, device="cuda")
-        out, _ = eng.play_refill(ev, seeds, records.data_ptr(), opponent_evaluator=ev_b, pairing=pairing)
+        out, _ = eng.play_refill(ev, seeds, records.data_ptr(), opponent_evaluator=ev_b, pairing=pairing,
+                                 reuse=bool(reuse and two))
         torch.cuda.synchronize()
         rec = records_to_numpy(records).reshape(num_games, _lib.MAX_PLIES)
     finally:

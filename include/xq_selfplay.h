@@ -364,8 +364,9 @@ int  xq_engine_refill_read_slots(xq_engine *e, int32_t *slot_game_host /*[G]*/);
  * network indexes the ONE set of planes the search kernel writes), leaf dedupe never shares a row between networks, and
  * xq_engine_eval_hashnet2 evaluates every pending leaf with its network's salt.  XQ_EVAL_PRIORS output stays indexed by
  * slot in the one priors / values array.  The evaluation cache and the root evaluation carry-over are refused by the
- * two-network calls (self-play slots of a mixed session run without them too).  The single-network calls are unchanged:
- * they ignore the pairing when choosing a network (the caller alternates by ply, as before) and number one row map. */
+ * two-network calls (self-play slots of a mixed session run without them too) unless xq_engine_set_per_slot_reuse
+ * (below) was switched on.  The single-network calls are unchanged: they ignore the pairing when choosing a network (the
+ * caller alternates by ply, as before) and number one row map. */
 /* pairing_host[g] for the game in slot g, now and for games xq_engine_new_games starts later (lock-step / set_roots
  * sessions); NULL = back to the default. */
 int  xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing_host /*[G]*/);
@@ -380,6 +381,24 @@ int  xq_engine_row_map_net(xq_engine *e, int net, const int32_t **row_src_dev, c
 /* xq_engine_read_row_history for the rows of one network (the two add up to the total) */
 int  xq_engine_read_row_history_net(xq_engine *e, int net, int32_t *rows_host, int cap, int64_t *n_rounds, int reset);
 int  xq_engine_eval_hashnet2(xq_engine *e, int salt0, int salt1);
+/* Opt-in (off until asked for): the root evaluation carry-over and the evaluation cache in two-network rounds and refill
+ * sessions - the trainer's epoch (trainer.py:186-209) in one session without giving up the two work eliminations of
+ * single-network play.  Neither has a counterpart in the reference, which rebuilds its tree every ply (self_play.py:98).
+ *   carry-over: decided per slot.  The played child's priors are those of the network that searched this ply; the next
+ *     root is searched by the same network exactly when the slot's pairing is 0.  xq_engine_play_move carries the root
+ *     of a pairing-0 slot as in single-network play; a pairing-1 slot's root stays "not ready" (it counts in
+ *     xq_engine_roots_not_ready) and round 0 evaluates it with the other network.
+ *   cache: the compared key holds the network a leaf waits for beside board and side, so one table serves both
+ *     networks (single-network rounds store and compare the bits they always did).  Only XQ_EVAL_LOGITS_* output is
+ *     cached, as before.
+ *   keep_plies: how long an entry lives, 2 or 3 (anything else: XQ_E_INVALID).  2 is the single-network window: one
+ *     network moves every ply.  In a pairing-1 game each network searches every second ply, so what network 0 evaluated
+ *     at ply p is wanted again at ply p + 2 - the root of ply p + 2 included, which no carry-over provides there: such
+ *     sessions want 3.
+ * With enable = 0 (the default) the two-network calls refuse both as before and entries live two plies.  Every other
+ * refusal stays: the carry-over with tree reuse, virtual loss, root noise or an opponent-mode engine.  Call before
+ * xq_engine_refill_begin2 / xq_engine_set_pairing / xq_engine_new_games; the call ages every cached entry out. */
+int  xq_engine_set_per_slot_reuse(xq_engine *e, int enable, int keep_plies);
 
 /* ---- network: fused 3x3 convolution of the residual tower (neural_network.py:54,181-187 with the
  * eval-mode BatchNorm folded into weights and bias):
