@@ -12,8 +12,10 @@
 // (bias [+ x], tap 0: ks 0..3, tap 1: ...) in k_tower16b's order: the results are the same bits.
 // Which pixel a column of the 6 pixel tiles carries is a table of the generator (PIX_OF), not 16 tile + column: the pixels of
 // file 0 sit in tile 5 beside the six empty columns, rank 0 and file 8 in tile 4, and the (pixel tile, tap) pairs in which
-// every column then reads the zero padding of the 3x3 convolution - the three left taps of tile 5, the upper right tap of
-// tile 4 - are not issued in taps 1..7: 96 of a layer's 1,728 MFMAs add exact zeros and are left out, same bits.
+// every column then reads the zero padding of the 3x3 convolution - the three left taps of tile 5 (tap 0 in the skewed first
+// tap, taps 3 and 6), the upper right tap of tile 4 - are not issued: 128 of a layer's 1,728 MFMAs add exact zeros and are
+// left out, same bits.  Tile 5's accumulators take the layer's bias row with the selector MFMA or, where the layer has none,
+// with (tap 1, K-step 0).
 // The parts outside the statement (input convolution, heads) are k_tower1w's HIP code: accumulators on literal AGPRs; the
 // input convolution and the 0-block epilogue follow the same column table, the heads read LDS by pixel in plain order.
 // The lane-dependent addresses the assembly needs (54 tap addresses, store addresses, selectors, DMA source offsets) are a
@@ -140,7 +142,7 @@ struct LaneTab1WA { int32_t v[256][XQ_1WA_TAB_DWORDS]; };
 
 // Which board pixel a column of a pixel tile carries (-1: none) is chosen by tools/gen_tower1wa.py (PIX_OF there): the file-0
 // pixels share tile 5 with the six empty columns, rank 0 and file 8 fill tile 4, so that whole (pixel tile, tap) pairs read
-// nothing but zero padding (XQ_1WA_DEAD_TAPS) and the body leaves their MFMAs out (XQ_1WA_SKIP_TAPS).  LDS rows stay indexed
+// nothing but zero padding (XQ_1WA_DEAD_TAPS) and the body leaves their MFMAs out (XQ_1WA_SKIP_TAPS: all of them).  LDS rows stay indexed
 // by the pixel; only the addresses below, the input convolution and the 0-block epilogue know the columns.
 struct PixTab1WA { int8_t p[6][16]; };
 constexpr PixTab1WA PIX_OF_1WA = { XQ_1WA_PIX_OF };

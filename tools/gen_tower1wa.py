@@ -13,13 +13,13 @@ that the compiler cannot interleave with.  What the assembly does that the HIP f
     the input channel group of 32, which is the output channel pair J = ks of the layer before.  As soon as pair J has
     been drained (accumulators -> bf16 -> ReLU -> LDS rows in place) and its accumulators hold the next layer's bias,
     the MFMAs of the next layer's tap 0 whose OUTPUT tiles are in a drained pair and whose INPUT group is a stored pair
-    can issue: group (P, K) = 12 MFMAs is ready after drain max(P, K).  Every accumulator still sees its K-steps in the
+    can issue: group (P, K) = 10 MFMAs is ready after drain max(P, K).  Every accumulator still sees its K-steps in the
     order (tap 0: ks 0, 1, 2, 3), (tap 1: ...) - the fp32 sums are the ones k_tower16b forms, bit for bit - but the
     drain's ~100 VALU + 18 LDS instructions per pair issue in the gaps of those MFMAs;
   * every s_waitcnt is an exact count (inserted by this script) and every hazard distance is checked;
   * the pixels are dealt to the MFMA columns (PIX_OF below) so that four (pixel tile, tap) pairs read nothing but the zero
-    padding of the 3x3 convolution; the three of them in taps 1..7 are not issued: 1,632 of a layer's 1,728 MFMAs, same bits
-    (a left-out MFMA adds +-0 to every accumulator; the ReLU on the bf16 bits maps both zeros to 0x0000).
+    padding of the 3x3 convolution; none of them is issued: 1,600 of a layer's 1,728 MFMAs, same bits (a left-out MFMA adds
+    +-0 to an accumulator that holds at least the bias; the ReLU on the bf16 bits maps both zeros to 0x0000).
 
 The script is also the kernel's checker: it runs the instruction stream of a 3-block tower through a symbolic model
 (LDS rows by (layer, pair) of the data they hold, ring slots by stage, fragment registers by what was loaded into
@@ -88,12 +88,13 @@ def tap_valid(p, tap):
 PIX_OF = _pix_of()                                                             # [tile][column] -> pixel 0..89 | PAD
 assert all(p is not None and (p == PAD or p & 7 == c & 7) for row in PIX_OF for c, p in enumerate(row))
 DEAD = frozenset((n, tap) for n in range(6) for tap in range(9) if not any(tap_valid(p, tap) for p in PIX_OF[n]))
-# the pairs the schedule leaves out: the ones of the regular taps.  (tile 5, tap 0) runs inside the skewed first tap and is
-# issued in the committed body; XQ_1WA_SKIP_TAP0=1 ("skew" schedule only) leaves it out too (Emitter.skew: its groups shrink
-# from 12 to 10 MFMAs; where the layer has no selector MFMA - the first convolution of a block - tile 5's first MFMA, the
-# one that takes the bias row as C, is then (tap 1, ks 0) in tap_regular).  Measured: DESIGN.md section 6.
-SKIP_TAP0 = os.environ.get("XQ_1WA_SCHEDULE", "skew") == "skew" and os.environ.get("XQ_1WA_SKIP_TAP0", "0") == "1"
-SKIP = frozenset((n, tap) for (n, tap) in DEAD if 1 <= tap <= 7 or (tap == 0 and SKIP_TAP0))
+# the pairs the schedule leaves out: all of them under the "skew" schedule (the product).  The three of the regular taps 1..7
+# fall out of tap_regular; (tile 5, tap 0) falls out of the skewed first tap (Emitter.skew: its groups are 10 MFMAs instead of
+# 12, and where the layer has no selector MFMA - a block's first convolution, entered behind the input convolution or the
+# block before - tile 5's first MFMA, the one that takes the bias row as C, is (tap 1, ks 0) in tap_regular).  The
+# alternative "transition" schedule does not implement the tap-0 omission and keeps the pairs of taps 1..7 only.
+# Measured: DESIGN.md section 6.
+SKIP = frozenset((n, tap) for (n, tap) in DEAD if 1 <= tap <= 7 or os.environ.get("XQ_1WA_SCHEDULE", "skew") == "skew")
 
 
 # ---- register plan ------------------------------------------------------------------------------------------------------
@@ -164,6 +165,7 @@ class Emitter:
         self.ins = []
         self.stamps = stamps
         self.nlabel = 0
+        Emitter.NVALU[0] = 0       # (the "valu<k>" probes: every block's instance of a section must be the same text)
 
     def add(self, text, kind="salu", **m):
         self.ins.append(Ins(text, kind, **m))
@@ -478,9 +480,13 @@ class Emitter:
 
     def skew(self, lt, lt_next, lbase_next, rx, bias_slot, bias_fetch_slot, bias_fetch_tag, bias_skip_last, stamp_k, lead_in=None, fine=None):
         """drain of layer lt (pairs 0..3) with tap 0 of layer lt_next (first local stage lbase_next) issued as its operands
-        become ready.  MFMA group (P, K) = output pair P x input group K, 12 MFMAs, ready after drain max(P, K); inside a
-        pair the input groups ascend, so every accumulator sees (tap 0: ks 0, 1, 2, 3) in order.  Segment J = the groups
-        that drain J makes ready; its MFMAs issue while drain J + 1 is emitted around them.
+        become ready.  MFMA group (P, K) = output pair P x input group K, ready after drain max(P, K); inside a pair the
+        input groups ascend, so every accumulator sees (tap 0: ks 0, 1, 2, 3) in order.  Segment J = the groups that drain J
+        makes ready; its MFMAs issue while drain J + 1 is emitted around them.
+        A group is 2 weight tiles x the pixel tiles whose tap 0 is not in SKIP: 10 MFMAs under the skew schedule, where
+        (tile 5, tap 0) reads only the zero row - no MFMA and no tap-0 activation fragment load for tile 5.  Its tiles then
+        take the bias row with the selector MFMA (rx) or, where the next layer has none, with (tap 1, ks 0) in tap_regular.
+        12 MFMAs if SKIP holds no tap-0 pair.
         Fragment slots: activation fragment (K, n) = slot 6 K + n (resident until its last group), weight fragments of
         group i = slots 24 + 2 (i mod 3)."""
         self.comment("---- epilogue of layer %s under tap 0 of layer %s" % (lt, lt_next))
