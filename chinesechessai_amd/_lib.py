@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libxq_hip.so")
 SOURCES = [os.path.join(CSRC, "xq_engine.hip"), os.path.join(CSRC, "xq_conv.hip"), os.path.join(CSRC, "xq_replay.hip"),
-           os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip")]
+           os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip"), os.path.join(CSRC, "xq_policy_loss.hip")]
 HEADERS = [os.path.join(CSRC, "xq_device.hpp"), os.path.join(CSRC, "xq_attack.hpp"), os.path.join(CSRC, "xq_mfma.hpp"), os.path.join(CSRC, "xq_tower_probes.hpp"),
            os.path.join(CSRC, "xq_tower1wa.hpp"), os.path.join(CSRC, "xq_tower1wa_body.inc"), os.path.join(CSRC, "xq_policy_fc1w_body.inc"),
            os.path.join(_HERE, "..", "include", "xq_selfplay.h"), os.path.join(_HERE, "..", "include", "xq_debug.h")]
@@ -204,6 +204,12 @@ _SIGNATURES = {
     "xq_replay_push_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "xq_replay_encode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_replay_read_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "xq_replay_encode_policy_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double,
+                                                C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 5),
+    "xq_policy_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    "xq_policy_loss_grad_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                          C.c_void_p, C.c_int64, C.c_int]),
     "xq_engine_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "xq_engine_profile_read": (C.c_int, [C.c_void_p] * 5),
 }

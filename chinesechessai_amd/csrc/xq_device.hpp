@@ -483,4 +483,24 @@ __device__ MoveResult wave_make_move(int8_t *bd, MState &s, int move, Hist &hist
     return res;
 }
 
+// NumPy float64 add.reduce (pairwise, 8 partial sums; n <= 128): the sum under pi = counts ** (1/T) / sum of
+// self_play.py:230-231, for the sampler (k_play_move) and for the replay buffer's policy targets
+__device__ inline double np_sum(const double *a, int n)
+{
+    if (n < 8) {
+        double res = 0.;
+        for (int i = 0; i < n; i++) res += a[i];
+        return res;
+    }
+    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8) {
+        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
+        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; i < n; i++) res += a[i];
+    return res;
+}
+
 }  // namespace xq

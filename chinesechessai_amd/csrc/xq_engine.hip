@@ -1549,25 +1549,6 @@ __global__ __launch_bounds__(64) void k_end_search(Eng E, EvalPair ev)
     }
 }
 
-// NumPy float64 add.reduce (pairwise, 8 partial sums; n <= 128)
-__device__ double np_sum(const double *a, int n)
-{
-    if (n < 8) {
-        double res = 0.;
-        for (int i = 0; i < n; i++) res += a[i];
-        return res;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8) {
-        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; i++) res += a[i];
-    return res;
-}
-
 // self_play.py:219-256 for every game: pi from root visits, sample record, np.random.choice on the
 // game's private MT19937 stream, make_move, and the next root's move list.
 __global__ __launch_bounds__(64) void k_play_move(Eng E)

@@ -9,7 +9,11 @@
 // Here the samples never leave HBM: the engine's xq_sample_record[] (or the all-gathered shards)
 // are compacted into a ring of records with the deque's drop-oldest semantics, and a batch is one
 // gather + encode kernel that writes float32 states [B][15][10][9] and targets [B][1] in place.
+// k_encode_policy is the same batch formation with the policy target beside it (the "完整版" of
+// trainer.py:327-331): pi = counts ** (1/T) / sum over the record's moves (self_play.py:234-239)
+// and the policy column of every move (neural_network.py:160), so that pi never leaves HBM either.
 #include "../../include/xq_selfplay.h"
+#include "xq_device.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
@@ -99,13 +103,92 @@ __global__ __launch_bounds__(64) void k_encode(const xq_sample_record *ring, int
     if (lane == 0) targets[b] = (float)r->z;
 }
 
+// Batch formation with the policy target.  states / targets as k_encode writes them (flags 0, player_mode 0: the same
+// bytes); cols / pi / n_moves as xq_replay_encode_policy_batch documents them.  Lane l carries move slots l and l + 64.
+// pi is the float64 arithmetic of k_play_move (xq_engine.hip), which restates distributed.record_to_sample: the powers
+// from the host's table (T == 1 needs none), np_sum, one division, then ONE rounding to float32.
+__global__ __launch_bounds__(64) void k_encode_policy(const xq_sample_record *ring, int64_t cap, int64_t head, const int64_t *idx,
+                                                      const uint8_t *flags, int player_mode, double temperature,
+                                                      const double *pow_table, const int32_t *column_map,
+                                                      float *states, float *targets, int32_t *cols, float *pi, int32_t *n_moves)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const xq_sample_record *r = ring + (size_t)((head + idx[b]) % cap);
+    const bool mirror = flags && (flags[b] & 1);
+    __shared__ int8_t bd[96];
+    __shared__ double fbuf[XQ_MAX_MOVES];
+    __shared__ double s_sum;
+    __shared__ int s_am;
+    if (lane < 12) {
+        const uint32_t w = r->board[lane];
+        for (int j = 0; j < 8; j++) {
+            const int s = 8 * lane + j;
+            const uint32_t code = (w >> (4 * j)) & 15u;
+            // file c -> 8 - c (squares 90..95 are nibble padding: they stay where they are)
+            const int d = (mirror && s < 90) ? s - s % 9 + 8 - s % 9 : s;
+            bd[d] = (int8_t)(code <= 7 ? (int)code : 7 - (int)code);
+        }
+    }
+    const int n = r->n_moves > XQ_MAX_MOVES ? XQ_MAX_MOVES : (int)r->n_moves;
+    int cnt[2];
+    for (int k = 0; k < 2; k++) {
+        const int j = lane + 64 * k;
+        cnt[k] = j < n ? (int)r->counts[j] : 0;
+        int col = -1;
+        if (j < n) {
+            int m = r->moves[j];
+            if (m < XQ_POLICY_SIZE) {                                   // (anything else is no move: it has no column)
+                if (mirror) {
+                    const int f = m / 90, t = m % 90;
+                    m = (f - f % 9 + 8 - f % 9) * 90 + (t - t % 9 + 8 - t % 9);
+                }
+                col = column_map ? column_map[m] : m;
+            }
+        }
+        cols[(size_t)b * XQ_MAX_MOVES + j] = col;
+        if (temperature >= 0.01 && j < n) {                             // self_play.py:230
+            const int c = cnt[k];
+            fbuf[j] = pow_table ? pow_table[c] : (double)c;                 // (no table: T == 1, checked on the host)
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        if (temperature < 0.01) {                                       // self_play.py:224-227: np.argmax, first maximum
+            int am = 0;
+            for (int j = 1; j < n; j++) if (r->counts[j] > r->counts[am]) am = j;
+            s_am = am;
+        } else {
+            s_sum = xq::np_sum(fbuf, n);
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < 2; k++) {
+        const int j = lane + 64 * k;
+        double p = 0.0;
+        if (j < n) p = temperature < 0.01 ? (j == s_am ? 1.0 : 0.0) : fbuf[j] / s_sum;
+        pi[(size_t)b * XQ_MAX_MOVES + j] = (float)p;
+    }
+    float *o = states + (size_t)b * 1350;
+    // plane 14: all ones (trainer.py:314 encodes every sample as red to move), or the record's side to move
+    const float plane14 = player_mode == 0 ? 1.0f : (r->player == 1 ? 1.0f : 0.0f);
+    for (int e = lane; e < 1350; e += 64) {
+        const int c = e / 90, s = e % 90;
+        float v;
+        if (c == 14) v = plane14;
+        else v = bd[s] == (c < 7 ? c + 1 : -(c - 6)) ? 1.0f : 0.0f;
+        o[e] = v;
+    }
+    if (lane == 0) { targets[b] = (float)r->z; n_moves[b] = n; }
+}
+
 struct Replay {
     int device;
     int64_t cap, head = 0, count = 0;
     xq_sample_record *ring = nullptr;
     int32_t *n_valid = nullptr;
     int64_t *offset = nullptr, *total = nullptr, *idx = nullptr;
-    int64_t n_games_cap = 0, idx_cap = 0;
+    uint8_t *flags = nullptr;
+    int64_t n_games_cap = 0, idx_cap = 0, flags_cap = 0;
 };
 
 thread_local std::string g_rerr;
@@ -141,6 +224,7 @@ extern "C" void xq_replay_destroy(void *h)
     if (!r) return;
     (void)hipSetDevice(r->device);
     (void)hipFree(r->ring); (void)hipFree(r->total); (void)hipFree(r->n_valid); (void)hipFree(r->offset); (void)hipFree(r->idx);
+    (void)hipFree(r->flags);
     delete r;
 }
 
@@ -196,6 +280,51 @@ extern "C" int xq_replay_encode_batch(void *h, void *stream, const int64_t *idx_
     RCHK(hipStreamSynchronize(s));
     hipLaunchKernelGGL(k_encode, dim3(batch), dim3(64), 0, s, r->ring, r->cap, r->head, r->idx, batch,
                        reinterpret_cast<float *>(states_dev), reinterpret_cast<float *>(targets_dev));
+    RCHK(hipGetLastError());
+    return 0;
+}
+
+/* xq_replay_encode_batch plus the policy target (cols, pi, n_moves): see include/xq_selfplay.h */
+extern "C" int xq_replay_encode_policy_batch(void *h, void *stream, const int64_t *idx_host, int batch, const uint8_t *flags_host,
+                                             int player_mode, double temperature, const void *pow_table_dev, int pow_n,
+                                             const void *column_map_dev, void *states_dev, void *targets_dev, void *cols_dev,
+                                             void *pi_dev, void *n_moves_dev)
+{
+    Replay *r = reinterpret_cast<Replay *>(h);
+    if (!r || !idx_host || batch <= 0 || !states_dev || !targets_dev || !cols_dev || !pi_dev || !n_moves_dev) return XQ_E_INVALID;
+    if (player_mode != 0 && player_mode != 1) { g_rerr = "player_mode must be 0 (red) or 1 (record)"; return XQ_E_INVALID; }
+    if (!(temperature >= 0.0)) { g_rerr = "temperature must not be negative"; return XQ_E_INVALID; }
+    if (temperature >= 0.01 && temperature != 1.0 && (!pow_table_dev || pow_n < 65536)) {
+        // (the device's pow is not NumPy's: the powers come from the host, as for the sampler, xq_engine_set_pow_table)
+        g_rerr = "a temperature other than 1 needs the host's table of counts ** (1/T) for all 65536 counts";
+        return XQ_E_INVALID;
+    }
+    for (int i = 0; i < batch; i++)
+        if (idx_host[i] < 0 || idx_host[i] >= r->count) { g_rerr = "index out of range"; return XQ_E_INVALID; }
+    RCHK(hipSetDevice(r->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (batch > r->idx_cap) {
+        (void)hipFree(r->idx);
+        r->idx = nullptr; r->idx_cap = 0;
+        RCHK(hipMalloc(&r->idx, (size_t)batch * 8));
+        r->idx_cap = batch;
+    }
+    if (flags_host && batch > r->flags_cap) {
+        (void)hipFree(r->flags);
+        r->flags = nullptr; r->flags_cap = 0;
+        RCHK(hipMalloc(&r->flags, (size_t)batch));
+        r->flags_cap = batch;
+    }
+    RCHK(hipMemcpyAsync(r->idx, idx_host, (size_t)batch * 8, hipMemcpyHostToDevice, s));
+    if (flags_host) RCHK(hipMemcpyAsync(r->flags, flags_host, (size_t)batch, hipMemcpyHostToDevice, s));
+    RCHK(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(k_encode_policy, dim3(batch), dim3(64), 0, s, r->ring, r->cap, r->head, r->idx,
+                       flags_host ? r->flags : nullptr, player_mode, temperature,
+                       pow_n >= 65536 ? reinterpret_cast<const double *>(pow_table_dev) : nullptr,
+                       reinterpret_cast<const int32_t *>(column_map_dev),
+                       reinterpret_cast<float *>(states_dev), reinterpret_cast<float *>(targets_dev),
+                       reinterpret_cast<int32_t *>(cols_dev), reinterpret_cast<float *>(pi_dev),
+                       reinterpret_cast<int32_t *>(n_moves_dev));
     RCHK(hipGetLastError());
     return 0;
 }

@@ -464,8 +464,54 @@ int     xq_replay_push_records(void *rb, void *hip_stream, const void *records_d
 /* states float32 [batch][15][10][9], targets float32 [batch][1] for deque indices idx_host[] */
 int     xq_replay_encode_batch(void *rb, void *hip_stream, const int64_t *idx_host, int batch, void *states_dev,
                                void *targets_dev);
+/* Batch formation with the policy target: the full version of trainer.py:313-331, whose loss uses the reward only
+ * ("完整版需要把move_probs转换为target policy").  Per deque index idx_host[b] it writes, without leaving HBM:
+ *   states  float32 [batch][15][10][9], targets float32 [batch][1]  as xq_replay_encode_batch does
+ *   pi      float32 [batch][128]  slot i = counts[i] ** (1/T) / sum over the record's moves (self_play.py:234-239),
+ *                                 formed in float64 as the sampler forms it and rounded once to float32; T < 0.01: 1.0
+ *                                 on the first maximum, 0 elsewhere (self_play.py:224-227); slots >= n_moves are 0
+ *   cols    int32   [batch][128]  slot i = policy column of moves[i]: the move index from*90+to itself
+ *                                 (neural_network.py:160) when column_map_dev is NULL, else column_map_dev[move]
+ *                                 (device int32[8100]: the table xq_engine_set_logit_columns takes as int16, e.g. of
+ *                                 the 2,304-column head); slots >= n_moves are -1; a move the map gives -1 keeps -1,
+ *                                 and so does a stored code that is no move (>= 8100)
+ *   n_moves int32   [batch]
+ * pow_table_dev (device float64[pow_n], pow_n >= 65536: one entry per uint16 count): counts ** (1/T) as the HOST's
+ * numpy evaluates it (as xq_engine_set_pow_table: the device's pow is not numpy's), required for every T >= 0.01
+ * other than 1 (XQ_E_INVALID without it); T == 1 and T < 0.01 need none (NULL / 0).
+ * flags_host (host uint8[batch], NULL = all 0): bit 0 mirrors the sample left-right (file c -> 8 - c): the board
+ * before it is encoded, `from` and `to` of every move before the column lookup; the order of the moves and pi are
+ * unchanged.  Xiangqi's rules are symmetric under that flip; the reference has no augmentation.
+ * player_mode 0: plane 14 is all ones (trainer.py:314 encodes every sample as red to move); 1: plane 14 is
+ * (record.player == 1): the engine stores +1 / -1, a record without a side (player 0, what ReplayBuffer.push of the
+ * host mirror writes) gets zeros.
+ * Indices are range-checked before any launch: XQ_E_INVALID and xq_replay_last_error. */
+int     xq_replay_encode_policy_batch(void *rb, void *hip_stream, const int64_t *idx_host, int batch,
+                                      const uint8_t *flags_host, int player_mode, double temperature,
+                                      const void *pow_table_dev, int pow_n, const void *column_map_dev, void *states_dev,
+                                      void *targets_dev, void *cols_dev, void *pi_dev, void *n_moves_dev);
 /* compatibility view: the records at deque indices idx_host[] copied to host memory */
 int     xq_replay_read_records(void *rb, void *hip_stream, const int64_t *idx_host, int batch, void *records_host);
+
+/* ------------------------------------------------------------------------------------------
+ * Policy loss: legal-move cross-entropy of the policy logits against the target xq_replay_encode_policy_batch
+ * writes, with the softmax the search applies (neural_network.py:148-169: over the legal moves only).
+ *     p = softmax(logits[b][cols[b][i]]) over the usable slots i < n_moves[b],  loss[b] = - sum_i pi[b][i] * log p_i
+ * logits float32 [batch][n_cols] with `row_stride` elements between rows; a slot whose column is -1 (or outside
+ * 0 .. n_cols-1) is unusable: it takes part in neither the softmax nor the sum.  fp32 arithmetic with the row maximum
+ * subtracted; a term with pi == 0 contributes exactly 0; reductions in a fixed order (a row's result does not depend
+ * on the batch or the launch).  Writes loss float32 [batch] and resid float32 [batch][128] = p_i - pi_i (0 at unusable
+ * slots); a row with no usable slot has loss 0 and residual 0.  All device pointers; launches on `hip_stream`.
+ * ------------------------------------------------------------------------------------------ */
+int  xq_policy_loss_f32(void *hip_stream, const void *logits_dev, int64_t row_stride, int n_cols, const void *cols_dev,
+                        const void *pi_dev, const void *n_moves_dev, int batch, void *loss_dev, void *resid_dev);
+/* Its gradient: grad float32 [batch][n_cols] (`row_stride` elements between rows; elements between n_cols and the
+ * stride are not touched) = scale[b] * resid at the columns of the usable slots and 0 everywhere else, in one pass in
+ * which every element is stored exactly once.  scale_dev: device float32 [batch], or NULL for scale_host on every row.
+ * 16-byte stores when grad_dev and row_stride keep every row 16-byte aligned, 4-byte stores otherwise. */
+int  xq_policy_loss_grad_f32(void *hip_stream, const void *resid_dev, const void *cols_dev, const void *n_moves_dev,
+                             const void *scale_dev, float scale_host, int batch, void *grad_dev, int64_t row_stride,
+                             int n_cols);
 
 /* ---- measurement: HIP events recorded on the engine's stream around the tree-kernel launches: enable = 0 off, 1 every
  * launch, N > 1 every N-th xq_engine_search_round (an event pair costs the GPU a few microseconds; every
