@@ -2800,6 +2800,25 @@ extern "C" int xq_engine_read_leaf_rows(xq_engine *e, int32_t *rows /*[G * leaf_
     return 0;
 }
 
+// diagnostic (include/xq_debug.h): the row map of the last search round as the evaluator kernels read it - *count_host =
+// row_count[net], row_src_host[0 .. min(cap, count)) = row_src of that network (the slot each row's planes are in)
+extern "C" int xq_engine_read_row_map(xq_engine *e, int net, int32_t *row_src_host, int cap, int32_t *count_host)
+{
+    if (!e || !count_host || cap < 0 || (cap > 0 && !row_src_host)) return fail(XQ_E_INVALID, "bad argument");
+    if (net < 0 || net > 1) return fail(XQ_E_INVALID, "net must be 0 or 1");
+    if (!e->E.compact) return fail(XQ_E_INVALID, "xq_engine_read_row_map: row compaction is off (there is no row map)");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int32_t count = 0;
+    HIPCHK(hipMemcpy(&count, e->E.row_count + net, 4, hipMemcpyDeviceToHost));
+    *count_host = count;
+    int take = count < cap ? count : cap;
+    if (take > e->E.n_slots) take = e->E.n_slots;                        // (never past the network's part of row_src)
+    if (take > 0)
+        HIPCHK(hipMemcpy(row_src_host, e->E.row_src + (size_t)net * e->E.n_slots, (size_t)take * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int xq_engine_eval_hashnet2(xq_engine *e, int salt0, int salt1)
 {
     if (!e) return fail(XQ_E_INVALID, "null engine");

@@ -21,8 +21,8 @@
 
 namespace {
 
-// records are [n_games][70]; the valid ones of game g are its first n_valid[g] plies (they were
-// pushed in game order, ply order: the order trainer.py:224 / ReplayBuffer.push would append them)
+// records are [n_games][70]; the valid ones of game g - the engine writes them as a prefix of its plies, the ABI
+// takes any subset - are pushed in game order, ply order: the order trainer.py:224 / ReplayBuffer.push would append them
 __global__ void k_count_valid(const xq_sample_record *rec, int n_games, int32_t *n_valid)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,10 +65,11 @@ __global__ void k_push(const xq_sample_record *rec, int n_games, const int64_t *
 {
     const int g = blockIdx.x;
     const size_t words = sizeof(xq_sample_record) / 16;                 // 36 x 16 B
-    for (int i = 0; i < XQ_MAX_PLIES; i++) {
+    int64_t k = offset[g] - 1;                                          // running index of the game's valid records:
+    for (int i = 0; i < XQ_MAX_PLIES; i++) {                            // k_count_valid counted every one of them, gaps or not
         const xq_sample_record *src = rec + (size_t)g * XQ_MAX_PLIES + i;
-        if (!src->valid) break;
-        const int64_t k = offset[g] + i;
+        if (!src->valid) continue;
+        k++;
         if (k < total - cap) continue;
         xq_sample_record *dst = ring + (size_t)((tail + k) % cap);
         for (size_t wd = threadIdx.x; wd < words; wd += blockDim.x)

@@ -457,6 +457,15 @@ class SelfPlayEngine:
         _lib.check(self.L.xq_engine_row_map_net(self.h, int(net), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def read_row_map(self, net=0):
+        """(row_src, count) of the last search round as the evaluator kernels read them (xq_engine_read_row_map, a
+        diagnostic read-back that synchronises): row_src int32[count] = the slot whose planes row r reads, for network
+        `net` of a per-slot session (a single-network round numbers every row in network 0)."""
+        src = np.zeros(self.n_rows, np.int32)
+        n = np.zeros(1, np.int32)
+        _lib.check(self.L.xq_engine_read_row_map(self.h, int(net), _lib.ptr(src), len(src), _lib.ptr(n)))
+        return src[:min(int(n[0]), len(src))].copy(), int(n[0])
+
     def row_history_net(self, net, cap=65536):
         """row_history() of one network: the rows that network's evaluator had to run in each of the last rounds (a
         single-network round counts as network 0's)."""

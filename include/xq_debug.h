@@ -77,6 +77,13 @@ void xq_engine_set_search_occupancy(int waves_per_simd);
  * 7 make_move done, 8 leaf record + planes stored, 9 dedupe insert done).  NULL switches them off.  Process-wide. */
 int  xq_engine_set_search_stamps(void *dev_u64x16_per_game);
 
+/* The row map of the last search round, read back (tests: the array the evaluator kernels read is otherwise never seen
+ * by the host).  Synchronises the engine's stream, as the other read-backs do; *count_host = the row count of network
+ * `net` (0 or 1; a single-network round numbers everything in network 0), row_src_host[0 .. min(cap, count)) = the slot
+ * whose planes each row reads.  XQ_E_INVALID while row compaction is off.  `e` is an xq_engine (xq_selfplay.h). */
+struct xq_engine;
+int  xq_engine_read_row_map(struct xq_engine *e, int net, int32_t *row_src_host, int cap, int32_t *count_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -443,7 +443,10 @@ int  xq_policy_fc_bf16(void *hip_stream, const void *act_dev, const void *w_dev,
 
 /* The value head behind its 1x1 convolution (neural_network.py:43-45,66-69): values[m] = tanh(fc2(relu(fc1(hv[m])))).
  * hv [n_rows][720] bf16 ((h, w, c) order, as xq_tower_nhwc_bf16 writes it) with at least 32 readable bytes behind
- * the last row; w1 [128][736] bf16 = value_fc1.weight with its input columns permuted to (h, w, c) and 16 zero
+ * the last row.  The 16 bf16 values behind each row the kernel computes are read and meet the 16 zero columns of w1:
+ * they must be FINITE (0 * NaN and 0 * Inf are NaN) - the first values of the next row, and behind the last computed
+ * row whatever the buffer holds there: under row compaction the first values of a stale row, behind the last row the
+ * slack, which the caller initialises once (zero, as InferenceNet's buffers do).  w1 [128][736] bf16 = value_fc1.weight with its input columns permuted to (h, w, c) and 16 zero
  * columns appended; b1, w2 float32[128]; b2 float32[1]; values bf16[n_rows].  The hidden layer stays in fp32.
  * n_rows_dev (optional, device int32): only rows below it are computed. */
 int  xq_value_head_bf16(void *hip_stream, const void *hv_dev, const void *w1_dev, const void *b1_dev, const void *w2_dev,
@@ -459,7 +462,8 @@ const char *xq_replay_last_error(void);
 int     xq_replay_create(int device, int64_t capacity, void **out);
 void    xq_replay_destroy(void *rb);
 int64_t xq_replay_size(void *rb);                       /* len(buffer) */
-/* push every valid record of records_dev [n_games][70] in game / ply order (drop-oldest) */
+/* push every valid record of records_dev [n_games][70] in game / ply order (drop-oldest); the valid records of a game
+ * need not be a prefix of its 70 plies: invalid ones in between are skipped, *n_pushed = the number of valid records */
 int     xq_replay_push_records(void *rb, void *hip_stream, const void *records_dev, int n_games, int64_t *n_pushed);
 /* states float32 [batch][15][10][9], targets float32 [batch][1] for deque indices idx_host[] */
 int     xq_replay_encode_batch(void *rb, void *hip_stream, const int64_t *idx_host, int batch, void *states_dev,
