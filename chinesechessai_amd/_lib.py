@@ -191,6 +191,8 @@ _SIGNATURES = {
     "xq_engine_read_row_history_net": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "xq_engine_eval_hashnet2": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "xq_engine_set_per_slot_reuse": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "xq_engine_set_playout_cap": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.c_int]),
+    "xq_engine_read_ply_sims": (C.c_int, [C.c_void_p, C.c_void_p]),
     "xq_conv3x3_nhwc_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int]),
     "xq_heads_nhwc_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int]),

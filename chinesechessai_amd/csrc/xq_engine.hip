@@ -142,6 +142,15 @@ struct Eng {
     // every round, [2][ROW_HIST]
     const uint8_t *pairing_init;
     int32_t *row_hist_net;
+    // ---- playout cap randomization (xq_engine_set_playout_cap; opt-in extension, KataGo, Wu 2019, §3.1): a ply is searched
+    // with E.sims simulations (a FULL ply) or with cap_fast of them (a FAST ply).  cap_fast == 0: off - nothing below is
+    // read, and the two arrays need not exist.  ply_sims[g] = the budget of the ply the game in slot g is at, decided by
+    // whatever starts a root (plan_ply); s_sims[g][i] = the budget stored sample i was searched with.
+    uint16_t *ply_sims;       // [G]
+    uint16_t *s_sims;         // [G][70]
+    uint64_t cap_seed;
+    uint32_t cap_thresh;      // round(full_prob * 2^24): a ply is full iff the top 24 bits of its hash lie below
+    int cap_fast, cap_record_fast;
 };
 
 // the evaluator outputs a tree kernel consumes, one per network (single-network launches: twice the same)
@@ -368,6 +377,20 @@ __device__ void backup(const Tree &T, int root, const uint16_t *path_node, int d
     mem_fence_wave();
 }
 
+// ---- playout cap randomization: the plan ------------------------------------------------------
+// The budget of ply `ply` of the game in slot g (call with E.cap_fast != 0 only).  Full or fast depends on the switch's
+// seed and on the game's own uniform for that ply - the double np.random.choice consumes later, which travels with the
+// game id through refill - and on nothing else: not on the slot, the refill order or the other games.  The host restates
+// it from the seeds (engine.playout_plan).  Every root's budget comes from here: new_game, k_set_roots, k_play_move (the
+// next ply), k_refill (through new_game, after the NEW game's uniforms are in place) and k_plan_roots.
+__device__ __forceinline__ int plan_ply(const Eng &E, int g, int ply)
+{
+    if (ply >= XQ_MAX_PLIES) return E.sims;          // (no such ply is searched: the rules end a game at 70)
+    const uint64_t bits = (uint64_t)__double_as_longlong(E.uniforms[(size_t)g * XQ_MAX_PLIES + ply]);
+    const uint64_t h = mix64(E.cap_seed ^ mix64(bits));
+    return (uint32_t)(h >> 40) < E.cap_thresh ? E.sims : E.cap_fast;
+}
+
 // ---- Dirichlet root noise (AlphaZero extension; absent from the reference) ------------------
 __device__ __forceinline__ float u01(uint64_t key)
 {
@@ -471,6 +494,9 @@ __device__ void consume_eval(const Eng &E, int g, int slot, WaveLds &L, const Tr
             if (lane == 0) { E.ec_stats[slot] += 1u; if (any) E.ec_stats[2 * E.ec_stat_stride + slot] += 1u; }
         }
     }
+    // (no playout-cap rule here: under the cap this function never meets a root - virtual loss refuses the cap, and
+    // k_end_search consumes a root only when a ply has one round, while the cap needs sims >= fast_sims > leaf_batch,
+    // i.e. two rounds at least: the root parked in round 0 is consumed by search_round_one<., true> in round 1)
     if (E.noise_eps > 0.0 && node == root) root_noise(E, g, ply, n, p0, p1);
     const int first = (int)E.n_nodes[g];
     if (first + n <= E.ncap) {
@@ -542,6 +568,7 @@ __device__ void new_game(const Eng &E, int g, WaveLds &L)
     if (lane == 0) {
         E.root_node[g] = 0;
         if (E.eval_carry) { E.root_ready[g] = 0; atomicAdd(E.roots_not_ready, 1); }
+        if (E.cap_fast) E.ply_sims[g] = (uint16_t)plan_ply(E, g, 0);     // (k_refill: lane 0 has stored the new game's uniform 0)
     }
 }
 
@@ -580,7 +607,22 @@ __global__ __launch_bounds__(64) void k_set_roots(Eng E, const int8_t *boards, c
             E.root_ready[g] = 0;
             atomicAdd(E.roots_not_ready, 1);
         }
+        if (E.cap_fast) E.ply_sims[g] = (uint16_t)plan_ply(E, g, 0);     // (the search on a caller's root is the game's ply 0)
     }
+}
+
+// playout cap: the budget of every slot's current ply again - after the switch was set, or after xq_engine_set_uniforms
+// replaced the streams the plan reads.  fill_stored (the switch goes from off to on): the samples the games in the slots
+// have stored so far were searched without the cap, i.e. with E.sims - nobody wrote s_sims for them, and pack_game
+// must not take them for fast plies.
+__global__ void k_plan_roots(Eng E, int fill_stored)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    const GameS gs = E.gs[g];
+    E.ply_sims[g] = (uint16_t)plan_ply(E, g, gs.n_plies);
+    if (fill_stored)
+        for (int i = 0; i < gs.n_samples && i < XQ_MAX_PLIES; i++) E.s_sims[(size_t)g * XQ_MAX_PLIES + i] = (uint16_t)E.sims;
 }
 
 // Leaf dedupe, first half (called by the wave that has just recorded a pending leaf in `slot`): look the position - the 12
@@ -984,7 +1026,11 @@ __device__ __forceinline__ int pick_child(int v0, int v1, int c)
 //       chosen child's move / flags need no memory at all.  Deeper levels walk memory as before (select_child).
 //   The leaf's packed board, its planes and the first look at the dedupe table leave right after the board is updated
 //   (wave_make_move's hook), so the table insert no longer waits a round trip behind ~3 KB of stores.
-template <bool STAMP>
+//   CAP: the playout-cap build of the round (xq_engine_set_playout_cap).  Launched only while the switch is on: the build
+//   every other launch runs holds none of its code - no load, no branch, no register (with the switch as a run-time
+//   flag in the one build: 127 -> 140 spilled SGPRs in the flagship kernel; 20 B of scratch with the budget held in a
+//   register across the round).
+template <bool STAMP, bool CAP>
 __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_count, const EvalPair &ev,
                                  void *planes, int fmt, unsigned long long *stamps)
 {
@@ -1013,6 +1059,8 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     const int lside = E.leaf_side[slot];
     int pair_v = 0;
     if (E.two_net) pair_v = E.pairing[g];            // (two-network rounds only: a single-network round issues what it always did)
+    int sims_v = 0;
+    if constexpr (CAP) sims_v = E.ply_sims[g];       // (the ply's budget, in the same round trip as everything else up here)
     int root = (round > 0 && E.tree_reuse) ? root_v : 0;
     int r_nc = T.nc[root], r_first = T.first[root];
     uint32_t r_N = T.N[root];
@@ -1029,6 +1077,12 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     const void *const ev_a = cnet ? ev.o[1].a : ev.o[0].a, *const ev_v = cnet ? ev.o[1].v : ev.o[0].v;
     const int ready = (round == 0 && E.eval_carry) ? ready_v : 0;
     int p_row = E.compact ? row_v : slot;
+    // playout cap: the round's simulations come out of the ply's own budget instead of the by-value count.  A slot whose
+    // budget is spent (count 0) still consumes its pending leaf below, then parks nothing: no row, nothing for the evaluator
+    if constexpr (CAP) {
+        const int left = uni(sims_v) - round * E.leaf_batch;
+        batch_count = left < 0 ? 0 : (left > E.leaf_batch ? E.leaf_batch : left);
+    }
     if (round == 0) p_node = LEAF_NONE;
     if (gs.done) return;
     if (ready) return;                               // k_play_move already built this ply's expanded root
@@ -1162,7 +1216,9 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
                 if (lane == 0) { E.ec_stats[slot] += 1u; if (any) E.ec_stats[2 * E.ec_stat_stride + slot] += 1u; }
             }
         }
-        if (E.noise_eps > 0.0 && p_node == root) root_noise(E, g, gs.n_plies, n, p0, p1);
+        // (playout cap: noise at full plies only - a fast ply's root priors are the network's bits)
+        // (the budget is read again here, on the noise path alone: held from the top it would cost every round a register)
+        if (E.noise_eps > 0.0 && p_node == root && (!CAP || uni((int)E.ply_sims[g]) == E.sims)) root_noise(E, g, gs.n_plies, n, p0, p1);
         const bool fits = p_first + n <= E.ncap;
         if (fits) {
             if (lane < n) {
@@ -1208,6 +1264,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     wave_sync();
     XQ_STAMP(2);
     XQ_STAMP(3);
+    if (CAP && batch_count <= 0) return;             // a fast ply past its budget: nothing to select, leaf_node stays LEAF_NONE
 
     // ---- select (self_play.py:117-119), first simulation of the round: level 0 from the registers (done in front of
     // the loop, so that the children's registers are dead before the move generation needs its own)
@@ -1353,7 +1410,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
 }
 
 // OCC = minimum waves per SIMD requested from the register allocator.
-template <int OCC, bool VL, bool STAMP = false>
+template <int OCC, bool VL, bool STAMP = false, bool CAP = false>
 __global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int batch_count, EvalPair ev, void *planes, int fmt,
                                                           unsigned long long *stamps = nullptr)
 {
@@ -1362,7 +1419,7 @@ __global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int 
     // slowest game)
     __shared__ WaveLds L;
     if constexpr (VL) search_round_generic<true>(E, L, round, batch_count, ev, planes, fmt);
-    else search_round_one<STAMP>(E, L, round, batch_count, ev, planes, fmt, stamps);
+    else search_round_one<STAMP, CAP>(E, L, round, batch_count, ev, planes, fmt, stamps);
 }
 
 __constant__ uint32_t c_crc_table[256];
@@ -1577,6 +1634,7 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
             E.s_counts[si * MAXM + j] = j < nc ? (uint16_t)L.ibuf[j] : 0;
         }
         if (lane == 0) { E.s_player[si] = gs.side; E.s_n[si] = (uint8_t)nc; }
+        if (E.cap_fast && lane == 0) E.s_sims[si] = E.ply_sims[g];      // the budget this ply was searched with (pack_game: fast plies)
     }
 
     // move probabilities and np.random.choice (serial float64, order matters)
@@ -1641,6 +1699,12 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
     // self_play.py:203,205-208,255-256: stop on done, on MAX_MOVES, or when nothing is legal
     gs.done = (mr.done || gs.n_plies >= E.max_moves || mr.n_legal == 0) ? 1 : 0;
     store_gs(E.gs + g, gs);
+    // playout cap: this kernel starts the next ply's root, so it decides that ply's budget
+    int next_sims = E.sims;
+    if (E.cap_fast) {
+        next_sims = plan_ply(E, g, gs.n_plies);
+        if (lane == 0) E.ply_sims[g] = (uint16_t)next_sims;
+    }
     if (E.eval_carry && !gs.done) {
         // The reference rebuilds its tree every ply and so evaluates the new root again, although the position
         // was evaluated during this ply's search: the played child has visits, hence was expanded from a network
@@ -1661,7 +1725,9 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
             if (j0 < n) { const int x = 1 + j0; T.N[x] = 0; T.W[x] = 0.0; T.P[x] = p0; T.mv[x] = m0; T.first[x] = 0; T.nc[x] = 0; T.fl[x] = 0; }
             if (j1 < n) { const int x = 1 + j1; T.N[x] = 0; T.W[x] = 0.0; T.P[x] = p1; T.mv[x] = m1; T.first[x] = 0; T.nc[x] = 0; T.fl[x] = 0; }
             if (lane == 0) {
-                const int b0 = E.sims < E.leaf_batch ? E.sims : E.leaf_batch;
+                // round 0's count of the NEXT ply: min(its budget, leaf_batch).  (With the playout cap a fast budget is
+                // above leaf_batch - xq_engine_set_playout_cap refuses anything else - so that is leaf_batch there too.)
+                const int b0 = next_sims < E.leaf_batch ? next_sims : E.leaf_batch;
                 T.N[0] = (uint32_t)b0; T.W[0] = 0.0; T.P[0] = 0.f; T.mv[0] = 0; T.first[0] = 1; T.nc[0] = (uint8_t)n; T.fl[0] = 0;
                 E.n_nodes[g] = (uint32_t)(1 + n); E.root_node[g] = 0;
             }
@@ -1705,7 +1771,10 @@ __device__ void pack_game(const Eng &E, int g, const GameS &gs, xq_sample_record
     for (int i = 0; i < XQ_MAX_PLIES; i++) {
         const size_t si = (size_t)g * XQ_MAX_PLIES + i;
         xq_sample_record *r = rec + i;
-        const bool valid = i < gs.n_samples;
+        const bool valid = i < gs.n_samples;             // a stored ply
+        // playout cap: a fast ply keeps its contents and says so in `pad`; it is no policy-training record (valid = 0,
+        // what xq_replay_push_records skips) unless the switch asked for fast plies to be recorded too
+        const bool fast = valid && E.cap_fast && E.s_sims[si] != (uint16_t)E.sims;
         if (lane < 12) r->board[lane] = valid ? E.s_board[si * 12 + lane] : 0u;
         for (int j = lane; j < MAXM; j += 64) {
             r->moves[j] = valid ? E.s_moves[si * MAXM + j] : 0;
@@ -1715,8 +1784,8 @@ __device__ void pack_game(const Eng &E, int g, const GameS &gs, xq_sample_record
             r->z = valid ? E.s_z[si] : 0.0;
             r->player = valid ? E.s_player[si] : 0;
             r->n_moves = valid ? E.s_n[si] : 0;
-            r->valid = valid ? 1 : 0;
-            r->pad = 0; r->pad2 = 0;
+            r->valid = (valid && (!fast || E.cap_record_fast)) ? 1 : 0;
+            r->pad = fast ? 1 : 0; r->pad2 = 0;
             r->chosen = valid ? E.t_move[si] : 0;
         }
     }
@@ -2126,6 +2195,9 @@ struct xq_engine {
     unsigned dd_tag = 0;                      // round tag of the leaf dedupe table (never 0: the cleared table's tag)
     unsigned ec_epoch = 16, ec_seq = 0;       // evaluation cache: ply counter (+E.ec_keep at every new set of roots), launch counter
     int slot_reuse = 0;                       // xq_engine_set_per_slot_reuse: two-network rounds may use the cache and the carry-over
+    bool pairing_second = false;              // some game of the session has pairing 1 (xq_engine_set_pairing / refill_begin2): no playout cap
+    bool two_net_round = false;               // the last search / end_search call of the games in the slots was a two-network one: no playout cap
+                                              // (host only: the kernel argument E.two_net is written where it always was)
     // The cache's key is the position (board + side), its payload the priors BY INDEX into the leaf's legal-move list - and
     // that list also depends on the two king caches.  Play from roots whose caches say where the kings stand keeps them so
     // (wave_make_move updates them on every king move and capture), so there the position fixes the list.  Roots handed to
@@ -2344,6 +2416,7 @@ extern "C" int xq_engine_new_games(xq_engine *e, const uint32_t *seeds)
     e->ec_roots_ok = true;                                               // (the start position: true king caches)
     eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
+    e->two_net_round = false;                                            // (no round of these games has run yet)
     hipLaunchKernelGGL(k_new_games, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2410,6 +2483,7 @@ extern "C" int xq_engine_set_tree_reuse(xq_engine *e, int enable)
     HIPCHK(hipSetDevice(e->cfg.device));
     Eng &E = e->E;
     if (enable && E.eval_carry) return fail(XQ_E_INVALID, "tree reuse cannot be combined with root evaluation carry-over");
+    if (enable && E.cap_fast) return fail(XQ_E_INVALID, "tree reuse cannot be combined with the playout cap (a kept subtree carries another ply's budget): xq_engine_set_playout_cap(e, 1, 0, 0, 0) first");
     E.tree_reuse = enable ? 1 : 0;
     E.want_check = (enable || E.nrounds >= 12) ? 1 : 0;      // (a kept subtree's paths reach 12 plies with any number of rounds)
     if (int rc = grow_nodes(e)) return rc;
@@ -2432,6 +2506,7 @@ extern "C" int xq_engine_set_virtual_loss(xq_engine *e, int enable)
     const int K = enable ? E.leaf_batch : 1;
     if (K > 64) return fail(XQ_E_INVALID, "virtual loss needs leaf_batch <= 64 (one lane per pending slot)");
     if (enable && E.eval_carry) return fail(XQ_E_INVALID, "virtual loss cannot be combined with root evaluation carry-over");
+    if (enable && E.cap_fast) return fail(XQ_E_INVALID, "virtual loss cannot be combined with the playout cap (its search round takes the count by value): xq_engine_set_playout_cap(e, 1, 0, 0, 0) first");
     HIPCHK(hipSetDevice(e->cfg.device));
     if (K != E.leaf_slots) {
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -2500,6 +2575,10 @@ extern "C" int xq_engine_set_uniforms(xq_engine *e, const double *u)
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemcpyAsync(e->E.uniforms, u, (size_t)e->E.G * XQ_MAX_PLIES * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->E.cap_fast) {                     // the playout plan reads these doubles: plan every slot's current ply again
+        hipLaunchKernelGGL(k_plan_roots, dim3((e->E.G + 255) / 256), dim3(256), 0, e->stream, e->E, 0);
+        HIPCHK(hipGetLastError());
+    }
     return 0;
 }
 
@@ -2518,6 +2597,7 @@ extern "C" int xq_engine_set_roots(xq_engine *e, const int8_t *boards, const int
         e->ec_roots_ok = king_caches_true(boards + g * 90, state[g * XQ_STATE_WORDS + XQ_S_RED_KING], state[g * XQ_STATE_WORDS + XQ_S_BLACK_KING]);
     eval_cache_apply(e);
     e->active_posted = 0;
+    e->two_net_round = false;
     hipLaunchKernelGGL(k_set_roots, dim3(e->E.G), dim3(64), 0, e->stream, e->E, e->stage_boards, e->stage_state);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2577,6 +2657,7 @@ extern "C" int xq_engine_set_search_stamps(void *dev_u64x16_per_game)
 // put the network into the cache's key and the pairing into the carry-over's condition
 static int two_net_ok(xq_engine *e)
 {
+    if (e->E.cap_fast) return fail(XQ_E_INVALID, "a two-network round cannot be combined with the playout cap (evaluation games are not capped): xq_engine_set_playout_cap(e, 1, 0, 0, 0) first");
     if (e->slot_reuse) return 0;
     if (e->E.ec_on || e->ec_want) return fail(XQ_E_INVALID, "a two-network round cannot use the evaluation cache (two networks answer differently for one position): xq_engine_set_eval_cache(e, 0)");
     if (e->E.eval_carry) return fail(XQ_E_INVALID, "a two-network round cannot use the root evaluation carry-over (the carried priors are the mover's network's)");
@@ -2596,6 +2677,7 @@ static int search_round_impl(xq_engine *e, int round, int eval_kind, const void 
     if (eval_kind1 != XQ_EVAL_PRIORS && ev_a1 && e->E.compact && !e->row_map_fetched)
         return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map_net (rows are compacted)");
     e->E.two_net = two ? 1 : 0;
+    e->two_net_round = two != 0;
     if (!planes_ok(e->cfg.planes_format)) return fail(XQ_E_INVALID, "bad planes_format");
     if (eval_kind != XQ_EVAL_PRIORS && ev_a && e->E.compact && !e->row_map_fetched)
         return fail(XQ_E_INVALID, "logits handed in by slot while row compaction is on: fetch xq_engine_row_map (rows are compacted) "
@@ -2622,6 +2704,9 @@ static int search_round_impl(xq_engine *e, int round, int eval_kind, const void 
 #define XQ_LAUNCH_SEARCH(OCC, VLB) hipLaunchKernelGGL((k_search_round<OCC, VLB>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, \
                                                     round, batch, evp, planes, fmt, (unsigned long long *)nullptr)
     if (e->E.vloss) XQ_LAUNCH_SEARCH(4, true);
+    else if (e->E.cap_fast)              // the playout-cap build: the round's count comes from ply_sims[g], not from `batch`
+        hipLaunchKernelGGL((k_search_round<4, false, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
+                           planes, fmt, (unsigned long long *)nullptr);
 #if XQ_TOWER_PROBES
     else if (g_search_stamps)
         hipLaunchKernelGGL((k_search_round<4, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
@@ -2841,6 +2926,7 @@ static int end_search_impl(xq_engine *e, int eval_kind, const void *ev_a, const 
     if (two) { if (int rc = two_net_ok(e)) return rc; }
     HIPCHK(hipSetDevice(e->cfg.device));
     e->E.two_net = two ? 1 : 0;
+    e->two_net_round = two != 0;
     e->E.ec_epoch = e->ec_epoch; e->E.ec_seq = ++e->ec_seq;
     const EvalPair evp{ { { ev_a, ev_v, eval_kind, 0 }, { ev_a1, ev_v1, eval_kind1, 0 } } };
     hipLaunchKernelGGL(k_end_search, dim3(e->E.G), dim3(64), 0, e->stream, e->E, evp);
@@ -2917,6 +3003,62 @@ extern "C" int xq_engine_set_per_slot_reuse(xq_engine *e, int enable, int keep_p
     return 0;
 }
 
+// Playout cap randomization (opt-in extension, default off; KataGo, Wu 2019, §3.1; no counterpart in the reference, which
+// gives every ply the same number of simulations, self_play.py:214): see Eng::ply_sims and plan_ply.  fast_sims == 0
+// switches it off: every launch then gets the arguments it always got.  Every refusal comes before any state changes.
+extern "C" int xq_engine_set_playout_cap(xq_engine *e, double full_prob, int fast_sims, uint64_t seed, int record_fast)
+{
+    if (!e) return fail(XQ_E_INVALID, "null engine");
+    Eng &E = e->E;
+    if (fast_sims == 0) { E.cap_fast = 0; E.cap_record_fast = 0; return 0; }
+    if (!(full_prob > 0.0 && full_prob <= 1.0)) return fail(XQ_E_INVALID, "playout cap: full_prob must lie in (0, 1]");
+    if (fast_sims <= E.leaf_batch)
+        return fail(XQ_E_INVALID, "playout cap: fast_sims must exceed leaf_batch (the first leaf_batch simulations of a ply all land on "
+                                  "the root: its children would get no visit and the move choice would meet NaN probabilities)");
+    if (fast_sims > E.sims) return fail(XQ_E_INVALID, "playout cap: fast_sims must not exceed sims");
+    if (E.vloss) return fail(XQ_E_INVALID, "the playout cap cannot be combined with virtual loss (its search round takes the count by value)");
+    if (E.tree_reuse) return fail(XQ_E_INVALID, "the playout cap cannot be combined with tree reuse (a kept subtree carries another ply's budget)");
+    if (E.opponent_mode || e->pairing_second || e->two_net_round)
+        return fail(XQ_E_INVALID, "the playout cap cannot be combined with a second network (opponent mode, a pairing-1 game or a "
+                                  "two-network round: evaluation games are not capped)");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (!E.ply_sims) {
+        if (dalloc(e, E.ply_sims, (size_t)E.G) || dalloc(e, E.s_sims, (size_t)E.G * XQ_MAX_PLIES)) {
+            E.ply_sims = nullptr;
+            return fail(XQ_E_HIP, "hipMalloc failed");
+        }
+    }
+    const int was_off = E.cap_fast == 0;
+    E.cap_seed = seed;
+    E.cap_thresh = (uint32_t)floor(full_prob * 16777216.0 + 0.5);
+    E.cap_fast = fast_sims; E.cap_record_fast = record_fast ? 1 : 0;
+    // the games in the slots now (if any) get the budget of the ply they are at, and - when the switch was off - the plies
+    // they have stored so far count as searched with `sims`, which they were; later roots plan themselves
+    hipLaunchKernelGGL(k_plan_roots, dim3((E.G + 255) / 256), dim3(256), 0, e->stream, E, was_off);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the budget every stored sample was searched with, [G][70] by sample index (0 behind a game's last sample); with the
+// switch off that is `sims` for every sample
+extern "C" int xq_engine_read_ply_sims(xq_engine *e, uint16_t *sims_host)
+{
+    if (!e || !sims_host) return fail(XQ_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const size_t G = (size_t)e->E.G;
+    std::vector<GameS> gs(G);
+    HIPCHK(hipMemcpyAsync(gs.data(), e->E.gs, G * sizeof(GameS), hipMemcpyDeviceToHost, e->stream));
+    if (e->E.cap_fast) HIPCHK(hipMemcpyAsync(sims_host, e->E.s_sims, G * XQ_MAX_PLIES * 2, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t g = 0; g < G; g++)
+        for (int i = 0; i < XQ_MAX_PLIES; i++) {
+            uint16_t &v = sims_host[g * XQ_MAX_PLIES + i];
+            if (i >= gs[g].n_samples) v = 0;
+            else if (!e->E.cap_fast) v = (uint16_t)e->E.sims;
+        }
+    return 0;
+}
+
 extern "C" int xq_engine_roots_not_ready(xq_engine *e, int32_t *n)
 {
     if (!e || !n) return fail(XQ_E_INVALID, "null argument");
@@ -2949,6 +3091,8 @@ extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int 
             if (pairing[i] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
             second |= pairing[i] != 0;
         }
+    if (second && e->E.cap_fast)
+        return fail(XQ_E_INVALID, "a refill session with a second network cannot be combined with the playout cap (evaluation games are not capped)");
     if (second && !e->slot_reuse && (e->E.eval_carry || e->ec_want))
         return fail(XQ_E_INVALID, "a refill session with a second network cannot use the evaluation cache or the root evaluation carry-over "
                                   "(xq_engine_set_per_slot_reuse allows both)");
@@ -2960,6 +3104,7 @@ extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int 
         e->refill_cap = total;
     }
     e->refill_pairs = pairing != nullptr;
+    e->pairing_second = second;
     if (pairing) HIPCHK(hipMemcpyAsync(e->pair_all, pairing, T, hipMemcpyHostToDevice, e->stream));   // (drained below)
     e->refill_total = total;                 // the session's size, every session: k_refill deals game ids below it only
     if (!e->slot_game && (dalloc(e, e->slot_game, G) || dalloc(e, e->next_game, (size_t)1)))
@@ -2980,6 +3125,7 @@ extern "C" int xq_engine_refill_begin2(xq_engine *e, const uint32_t *seeds, int 
     e->ec_roots_ok = true;                                               // (the start position: true king caches)
     eval_cache_apply(e);
     e->active_posted = 0;                                                // (a count posted for the last games says nothing about these)
+    e->two_net_round = false;                                            // (no round of these games has run yet)
     hipLaunchKernelGGL(k_new_games, dim3(e->E.G), dim3(64), 0, e->stream, e->E);
     HIPCHK(hipGetLastError());
     // the first G games sit in slot = id (k_new_games gave them what lock-step games get)
@@ -3007,6 +3153,8 @@ extern "C" int xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing)
             if (pairing[g] > 1) return fail(XQ_E_INVALID, "pairing must be 0 (self-play) or 1 (network 0 red vs network 1 black)");
             second |= pairing[g] != 0;
         }
+    if (second && e->E.cap_fast)
+        return fail(XQ_E_INVALID, "a second network cannot be combined with the playout cap (evaluation games are not capped)");
     if (second && !e->slot_reuse && (e->E.eval_carry || e->ec_want))
         return fail(XQ_E_INVALID, "a second network cannot be combined with the evaluation cache or the root evaluation carry-over "
                                   "(xq_engine_set_per_slot_reuse allows both)");
@@ -3015,6 +3163,7 @@ extern "C" int xq_engine_set_pairing(xq_engine *e, const uint8_t *pairing)
     else HIPCHK(hipMemsetAsync(e->pairing_init, e->E.opponent_mode ? 1 : 0, G, e->stream));
     HIPCHK(hipMemcpyAsync(e->E.pairing, e->pairing_init, G, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));          // (the caller's array may go away)
+    e->pairing_second = second;
     return 0;
 }
 

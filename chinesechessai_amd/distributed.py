@@ -13,6 +13,8 @@ from . import _lib
 from .chess_env import decode_move
 
 RECORD_BYTES = _lib.SAMPLE_RECORD_BYTES           # sizeof(xq_sample_record) = 576
+# "pad": 1 = a FAST ply of a playout-capped game (SelfPlayEngine.set_playout_cap), searched with fast_sims simulations;
+# such a record has valid = 0 - the replay buffer skips it - unless the cap was set with record_fast.  0 otherwise.
 RECORD_DTYPE = np.dtype([("board", "<u4", (12,)), ("z", "<f8"), ("player", "i1"), ("n_moves", "u1"),
                          ("valid", "u1"), ("pad", "u1"), ("chosen", "<u2"), ("pad2", "<u2"),
                          ("moves", "<u2", (128,)), ("counts", "<u2", (128,))])

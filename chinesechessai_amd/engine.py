@@ -60,6 +60,49 @@ def normalise_pairing(pairing, total, has_opponent):
     return p
 
 
+def _mix64(x):
+    """mix64 of csrc/xq_device.hpp on a uint64 array (arithmetic modulo 2^64)"""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xbf58476d1ce4e5b9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94d049bb133111eb)
+    return x ^ (x >> np.uint64(31))
+
+
+def playout_cap_threshold(full_prob):
+    """round(full_prob * 2^24) as xq_engine_set_playout_cap forms it: floor(x + 0.5) in float64"""
+    return int(np.floor(np.float64(full_prob) * 16777216.0 + 0.5))
+
+
+def playout_plan(uniforms, seed, full_prob):
+    """The playout cap's plan, restated on the host (xq_engine_set_playout_cap): bool array of uniforms' shape, True =
+    the ply is searched FULLY.  uniforms[..., ply] are the doubles np.random.choice consumes - for game seed s the first
+    70 of np.random.RandomState(s).random_sample - so a game's plan depends on its own seed and the switch's seed only."""
+    u = np.ascontiguousarray(uniforms, dtype=np.float64)
+    h = _mix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ _mix64(u.view(np.uint64)))
+    return (h >> np.uint64(40)) < np.uint64(playout_cap_threshold(full_prob))
+
+
+def normalise_playout_cap(playout_cap):
+    """parallel_self_play / self_play_epoch(playout_cap=...): None, (full_prob, fast_sims) or a dict with those keys and
+    optionally seed / record_fast -> None or the keyword arguments of SelfPlayEngine.set_playout_cap"""
+    if playout_cap is None:
+        return None
+    if isinstance(playout_cap, dict):
+        extra = set(playout_cap) - {"full_prob", "fast_sims", "seed", "record_fast"}
+        if extra or "full_prob" not in playout_cap or "fast_sims" not in playout_cap:
+            raise ValueError("playout_cap: a dict needs full_prob and fast_sims (optional: seed, record_fast), got %r" % (playout_cap,))
+        kw = dict(playout_cap)
+    else:
+        try:
+            full_prob, fast_sims = playout_cap
+        except (TypeError, ValueError):
+            raise ValueError("playout_cap must be (full_prob, fast_sims) or a dict, got %r" % (playout_cap,))
+        kw = {"full_prob": full_prob, "fast_sims": fast_sims}
+    return {"full_prob": float(kw["full_prob"]), "fast_sims": int(kw["fast_sims"]), "seed": int(kw.get("seed", 0)),
+            "record_fast": bool(kw.get("record_fast", False))}
+
+
 class HashNetEvaluator:
     """SURVEY.md Appendix B evaluator, on the GPU."""
     planes_format = _lib.PLANES_NONE
@@ -305,6 +348,7 @@ class SelfPlayEngine:
         self.reuse_keep_plies = None                            # play_refill(reuse=True): None = 3 when a game has pairing 1, else 2
         self._noise = self._vloss = False
         self.tree_reuse = False
+        self.playout_cap = None                                 # set_playout_cap: (full_prob, fast_sims, seed, record_fast)
         if stream is not None:
             _lib.check(self.L.xq_engine_set_stream(h, C.c_void_p(stream)))
         if temperature >= 0.01 and temperature != 1.0:
@@ -608,6 +652,26 @@ class SelfPlayEngine:
         self.priors_ptr = self.L.xq_engine_priors_ptr(self.h)
         self.values_ptr = self.L.xq_engine_values_ptr(self.h)
 
+    def set_playout_cap(self, full_prob, fast_sims, seed=0, record_fast=False):
+        """Playout cap randomization (extension, xq_engine_set_playout_cap; KataGo, Wu 2019, §3.1): every ply is searched
+        with `sims` simulations with probability full_prob (a FULL ply), else with fast_sims (a FAST ply; leaf_batch <
+        fast_sims <= sims).  Full or fast is decided by `seed` and the game's own uniform of that ply - playout_plan()
+        restates it on the host.  Every ply is still stored (read_results / game_data keep them all, and ply_sims() says
+        which was which); in the packed records (pack_samples, play_refill) a fast ply has pad = 1 and valid = 0, so the
+        replay buffer trains its policy on fully searched plies only - unless record_fast.  Root noise is added at full
+        plies only.  fast_sims = 0 switches it off.  Raises together with virtual loss, tree reuse, an opponent-mode
+        engine or a second network.  Call before new games start."""
+        _lib.check(self.L.xq_engine_set_playout_cap(self.h, float(full_prob), int(fast_sims), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                    1 if record_fast else 0))
+        self.playout_cap = None if int(fast_sims) == 0 else (float(full_prob), int(fast_sims), int(seed), bool(record_fast))
+
+    def ply_sims(self):
+        """uint16 [G, 70]: the simulations every stored sample was searched with (xq_engine_read_ply_sims; 0 behind a
+        game's last sample, `sims` everywhere without the playout cap)"""
+        s = np.zeros((self.n_games, _lib.MAX_PLIES), np.uint16)
+        _lib.check(self.L.xq_engine_read_ply_sims(self.h, _lib.ptr(s)))
+        return s
+
     def tree_stats(self):
         """(nodes in each game's arena, pending virtual-loss visits) — xq_engine_tree_stats."""
         n, v = np.zeros(self.n_games, np.int32), np.zeros(self.n_games, np.int32)
@@ -666,6 +730,8 @@ class SelfPlayEngine:
         """Play G games to the end (self_play_game for every game).  `seeds[g]` seeds game g's
         MT19937 stream like np.random.seed; `uniforms` overrides the streams.
         `temperature_schedule(ply) -> T` (extension) overrides the constant temperature per ply."""
+        if self.playout_cap and opponent_evaluator is not None:
+            raise _lib.XqError("the playout cap cannot be combined with a second network (evaluation games are not capped)")
         carry = self._auto_carry(evaluator, opponent_evaluator)
         self._bind(evaluator, opponent_evaluator)
         self.new_games(seeds)
@@ -721,6 +787,8 @@ class SelfPlayEngine:
             check_per_slot_evaluators(evaluator, opponent_evaluator)
         elif self.opponent_mode:
             raise _lib.XqError("play_refill on an opponent-mode engine needs opponent_evaluator")
+        if self.playout_cap and two:
+            raise _lib.XqError("the playout cap cannot be combined with a second network (evaluation games are not capped)")
         reuse = bool(reuse and two)
         if reuse or self._slot_reuse:        # (a session that never asked for it makes no call)
             self.set_per_slot_reuse(reuse, keep_plies=(self.reuse_keep_plies or (3 if pairing.any() else 2)) if reuse else 2)
@@ -775,6 +843,8 @@ class SelfPlayEngine:
         _lib.check(self.L.xq_engine_read_samples(self.h, _lib.ptr(b.s_board), _lib.ptr(b.s_player), _lib.ptr(b.s_n),
                                                  _lib.ptr(b.s_moves), _lib.ptr(b.s_counts), _lib.ptr(b.s_z),
                                                  _lib.ptr(b.chosen), _lib.ptr(b.step_reward)))
+        if self.playout_cap:
+            b.ply_sims = self.ply_sims()                        # which stored ply was searched fully, which fast
         return b
 
     def read_game_outcomes(self):

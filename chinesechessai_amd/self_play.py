@@ -14,7 +14,7 @@ from . import _lib
 from .chess_env import ChineseChess, decode_move, format_end_reason, _sq
 from .config import MAX_MOVES, MCTS_SIMULATIONS
 from .engine import (CallbackEvaluator, HashNetEvaluator, SelfPlayEngine, TorchNetEvaluator, check_per_slot_evaluators,
-                     check_reuse_evaluators, normalise_pairing)
+                     check_reuse_evaluators, normalise_pairing, normalise_playout_cap)
 
 
 class InterruptedWithResults(Exception):
@@ -169,8 +169,11 @@ class MCTS:
 
 
 def _play_batch(network, num_games, temperature, num_simulations, opponent_network, seeds=None, uniforms=None,
-                inference_dtype=None, partial_on_interrupt=False):
+                inference_dtype=None, partial_on_interrupt=False, playout_cap=None):
     sims = num_simulations if num_simulations else MCTS_SIMULATIONS
+    cap = normalise_playout_cap(playout_cap)
+    if cap is not None and opponent_network is not None:                       # (before any engine exists)
+        raise ValueError("playout_cap cannot be combined with an opponent network (evaluation games are not capped)")
     ev = _evaluator_for(network, inference_dtype=inference_dtype)
     ev_b = _evaluator_for(opponent_network, inference_dtype=inference_dtype) if opponent_network is not None else None
     if ev_b is not None and getattr(ev_b, "planes_format", 0) != getattr(ev, "planes_format", 0):
@@ -181,6 +184,8 @@ def _play_batch(network, num_games, temperature, num_simulations, opponent_netwo
     if seeds is None:
         seeds = np.random.randint(0, 2 ** 31 - 1, size=num_games).astype(np.uint32)
     try:
+        if cap is not None:
+            eng.set_playout_cap(**cap)
         return eng.play(ev, seeds, opponent_evaluator=ev_b, uniforms=uniforms)
     except KeyboardInterrupt:
         if not partial_on_interrupt:
@@ -231,14 +236,19 @@ def self_play_game(network, temperature=1.0, render=False, num_simulations=None,
 
 
 def parallel_self_play(network, num_games, temperature=1.0, num_simulations=None, num_workers=4,
-                       opponent_network=None, seeds=None, inference_dtype=None):
+                       opponent_network=None, seeds=None, inference_dtype=None, playout_cap=None):
     """self_play.py:368-469.  The reference's process pool becomes G concurrent games on the GPU;
     `num_workers` is accepted and ignored.  Results come back in game order (the reference's
     order is arbitrary: imap_unordered).  Ctrl-C raises InterruptedWithResults(results) with the
     games that had already finished (self_play.py:436-452); `inference_dtype` ("bf16" | "f32", default
-    INFERENCE_DTYPE) picks the precision a CUDA ChessNet is evaluated in."""
+    INFERENCE_DTYPE) picks the precision a CUDA ChessNet is evaluated in.
+    `playout_cap` (extension): (full_prob, fast_sims) or a dict with those keys and optionally seed / record_fast -
+    SelfPlayEngine.set_playout_cap: a ply is searched with num_simulations only with probability full_prob, else with
+    fast_sims.  The tuples returned here keep EVERY ply, fast ones included: this is the reference's return type, and
+    view_best_games replays a game by it; a trainer that wants fully searched plies only takes self_play_epoch's
+    records.  Raises ValueError with an opponent network."""
     batch = _play_batch(network, num_games, temperature, num_simulations, opponent_network, seeds=seeds,
-                        inference_dtype=inference_dtype, partial_on_interrupt=True)
+                        inference_dtype=inference_dtype, partial_on_interrupt=True, playout_cap=playout_cap)
     return batch.results()
 
 
@@ -253,7 +263,7 @@ def epoch_pairing(num_games, has_opponent):
 
 
 def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, opponent_network=None, slots=None,
-                    seeds=None, reuse=False):
+                    seeds=None, reuse=False, playout_cap=None):
     """The self-play of one trainer epoch (trainer.py:186-209: parallel_self_play(model, num_games // 2) and then
     parallel_self_play(model, num_games - num_games // 2, opponent_network=old_model)) in ONE refill session: both
     kinds of game go through the same `slots` concurrent slots and a finished game's slot takes the next game at once,
@@ -263,7 +273,11 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
     game's seed (failed games are dropped as there).  `seeds`: one per game (default: drawn from np.random).
     `reuse=True`: the session keeps the root evaluation carry-over (its self-play slots) and the evaluation cache (both
     networks, three-ply window) that a two-network session otherwise gives up (SelfPlayEngine.set_per_slot_reuse);
-    results are the same.  Without an opponent it changes nothing."""
+    results are the same.  Without an opponent it changes nothing.
+    `playout_cap` (extension, as in parallel_self_play): the session's packed records - what a replay buffer is fed,
+    ReplayBuffer.push_records - mark a fast ply with pad = 1 and valid = 0 (valid = 1 with record_fast), so its policy
+    target is never trained on; the tuples returned here are made from the records that are valid.  Raises ValueError
+    with an opponent network: two-network sessions refuse the cap."""
     num_games = int(num_games)
     if num_games < 1:
         raise ValueError("self_play_epoch: num_games must be at least 1")
@@ -277,6 +291,9 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
     if seeds.shape != (num_games,):
         raise ValueError("self_play_epoch: seeds must hold one entry per game")
     two = opponent_network is not None
+    cap = normalise_playout_cap(playout_cap)
+    if cap is not None and two:
+        raise ValueError("self_play_epoch: playout_cap cannot be combined with an opponent network (two-network sessions refuse the cap)")
     pairing = normalise_pairing(epoch_pairing(num_games, two), num_games, two) if two else None
     ev = _evaluator_for(network)
     ev_b = _evaluator_for(opponent_network) if two else None
@@ -294,6 +311,8 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
                          planes_format=getattr(ev, "planes_format", _lib.PLANES_NONE))
     try:
         records = torch.zeros(num_games * _lib.MAX_PLIES * RECORD_BYTES, dtype=torch.uint8, device="cuda")
+        if cap is not None:
+            eng.set_playout_cap(**cap)
         out, _ = eng.play_refill(ev, seeds, records.data_ptr(), opponent_evaluator=ev_b, pairing=pairing,
                                  reuse=bool(reuse and two))
         torch.cuda.synchronize()
@@ -304,7 +323,8 @@ def self_play_epoch(network, num_games, temperature=1.0, num_simulations=None, o
     for g in range(num_games):
         if out["error"][g]:
             continue
-        data = [record_to_sample(rec[g, i], temperature) for i in range(int(out["n_samples"][g]))]
+        # (a capped session: fast plies are stored but not valid; without the cap every stored record is valid)
+        data = [record_to_sample(rec[g, i], temperature) for i in range(int(out["n_samples"][g])) if rec[g, i]["valid"]]
         reason = format_end_reason(int(out["reason"][g]), int(out["reason_side"][g]), int(out["reason_count"][g]))
         results.append((data, int(out["winner"][g]), reason if reason else "未知原因"))
     return results

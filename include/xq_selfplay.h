@@ -258,8 +258,8 @@ typedef struct {
     double   z;
     int8_t   player;
     uint8_t  n_moves;
-    uint8_t  valid;
-    uint8_t  pad;
+    uint8_t  valid;           /* a record to train on (a fast ply of a capped game: 0 unless record_fast) */
+    uint8_t  pad;             /* 1 = a FAST ply of xq_engine_set_playout_cap (searched with fast_sims), else 0 */
     uint16_t chosen;
     uint16_t pad2;
     uint16_t moves[XQ_MAX_MOVES];
@@ -399,6 +399,45 @@ int  xq_engine_eval_hashnet2(xq_engine *e, int salt0, int salt1);
  * refusal stays: the carry-over with tree reuse, virtual loss, root noise or an opponent-mode engine.  Call before
  * xq_engine_refill_begin2 / xq_engine_set_pairing / xq_engine_new_games; the call ages every cached entry out. */
 int  xq_engine_set_per_slot_reuse(xq_engine *e, int enable, int keep_plies);
+
+/* ---- playout cap randomization (opt-in, off until asked for; KataGo, Wu 2019, section 3.1; NO counterpart in the reference,
+ * which searches every ply with the same number of simulations, self_play.py:214).  Each ply is searched FULLY - with the
+ * engine's `sims` simulations - with probability full_prob, else FAST with fast_sims simulations; only fully searched plies
+ * become policy-training records.  Games finish several times faster at the same compute: more independent games and value
+ * targets.
+ *   plan: full or fast depends on `seed` and on the game's own uniform for that ply - uniforms[g][ply], the double
+ *     np.random.choice consumes later (xq_engine_set_uniforms), which travels with the game id through refill - and on
+ *     nothing else (not the slot, the refill order or the other games):
+ *         h = mix64(seed ^ mix64(bits of the double)),  mix64(x): x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27;
+ *                                                                  x *= 0x94d049bb133111eb; x ^= x >> 31
+ *         full  iff  (h >> 40) < floor(full_prob * 2^24 + 0.5)
+ *     so the host can restate a game's plan from its seed.  Whatever starts a root decides that ply's budget:
+ *     xq_engine_new_games, xq_engine_play_move (the next ply), xq_engine_set_roots (the search on a caller's root is ply 0),
+ *     the refill (from the NEW game's uniform); this call and xq_engine_set_uniforms plan the current roots again.
+ *   search: round r of a ply runs clamp(budget - r * leaf_batch, 0, leaf_batch) simulations.  The caller's loop over
+ *     xq_engine_rounds_per_move rounds and xq_engine_end_search stay as they are: a slot whose budget is spent consumes its
+ *     pending leaf and parks nothing - with row compaction it is no evaluator row.  A root carried over
+ *     (xq_engine_set_root_eval_carry) starts with visit_count = min(budget of the next ply, leaf_batch) = leaf_batch.
+ *   root noise (xq_engine_set_root_noise) is added at full plies only; a fast ply's root priors are the network's bits.
+ *   records: every ply is still stored at its sample index; n_samples, the z table and its length thresholds are what they
+ *     are without the switch.  xq_engine_read_ply_sims: the budget every stored sample was searched with, uint16 [G][70]
+ *     (0 behind a game's last sample; `sims` everywhere while the switch is off).  In a packed xq_sample_record a fast
+ *     ply has pad = 1 and, unless record_fast != 0, valid = 0 - so xq_replay_push_records skips it - with all other fields
+ *     filled in; a full ply's record is what it is without the switch.
+ * Call it before xq_engine_new_games / xq_engine_set_roots / xq_engine_refill_begin.  Called while games are in the slots it
+ * takes effect from the ply they are at: the plies they stored while the switch was off were searched with `sims` and are
+ * recorded as that (full plies), and every slot's current ply gets its budget by the plan at once - so call it between
+ * xq_engine_play_move and the next ply's round 0, never between the rounds of a ply.  Calling it again while it is on (another seed, full_prob,
+ * fast_sims or record_fast) keeps what is stored and plans the current ply afresh.
+ * full_prob in (0, 1]; leaf_batch < fast_sims <= sims (at or below leaf_batch the root's children would get no visit and
+ * xq_engine_play_move would meet the reference's NaN error); fast_sims = 0 switches the feature off, and then every launch
+ * gets the arguments it always got.  fast_sims == sims and full_prob == 1 are the switch in name only: results equal a
+ * run without it.  XQ_E_INVALID, in whichever order the calls come, together with virtual loss, tree reuse, an
+ * opponent_mode engine, a pairing-1 game (xq_engine_set_pairing / xq_engine_refill_begin2) and the two-network calls
+ * (xq_engine_search_round2 / xq_engine_end_search2): evaluation games are not capped.  Works with row compaction, leaf
+ * dedupe, the root carry-over, the evaluation cache, refill and per-ply temperatures. */
+int  xq_engine_set_playout_cap(xq_engine *e, double full_prob, int fast_sims, uint64_t seed, int record_fast);
+int  xq_engine_read_ply_sims(xq_engine *e, uint16_t *sims_host /*[G][70]*/);
 
 /* ---- network: fused 3x3 convolution of the residual tower (neural_network.py:54,181-187 with the
  * eval-mode BatchNorm folded into weights and bias):
