@@ -12,8 +12,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libxq_hip.so")
 SOURCES = [os.path.join(CSRC, "xq_engine.hip"), os.path.join(CSRC, "xq_conv.hip"), os.path.join(CSRC, "xq_replay.hip"),
-           os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip"), os.path.join(CSRC, "xq_policy_loss.hip")]
-HEADERS = [os.path.join(CSRC, "xq_device.hpp"), os.path.join(CSRC, "xq_attack.hpp"), os.path.join(CSRC, "xq_mfma.hpp"), os.path.join(CSRC, "xq_tower_probes.hpp"),
+           os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip"), os.path.join(CSRC, "xq_policy_loss.hip"),
+           os.path.join(CSRC, "xq_tower256.hip")]
+# per-source flags: the 256-channel trunk is compiled without packed fp32 arithmetic (it has no use for it)
+SOURCE_FLAGS = {"xq_tower256.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+HEADERS = [os.path.join(CSRC, "xq_device.hpp"), os.path.join(CSRC, "xq_attack.hpp"), os.path.join(CSRC, "xq_mfma.hpp"), os.path.join(CSRC, "xq_tower_args.hpp"), os.path.join(CSRC, "xq_tower_probes.hpp"),
            os.path.join(CSRC, "xq_tower1wa.hpp"), os.path.join(CSRC, "xq_tower1wa_body.inc"), os.path.join(CSRC, "xq_policy_fc1w_body.inc"),
            os.path.join(_HERE, "..", "include", "xq_selfplay.h"), os.path.join(_HERE, "..", "include", "xq_debug.h")]
 
@@ -81,7 +84,7 @@ def build(force=False, verbose=False):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if force or not os.path.exists(obj) or any(os.path.getmtime(obj) < os.path.getmtime(d) for d in [src] + headers):
             tower_rebuilt = tower_rebuilt or src.endswith("xq_tower.hip")
-            cmd = [hipcc_path()] + flags + ["-c", "-o", obj, src]
+            cmd = [hipcc_path()] + flags + SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", "-o", obj, src]
             if verbose:
                 print(" ".join(cmd))
             jobs.append((cmd, subprocess.Popen(cmd)))
@@ -197,6 +200,7 @@ _SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int]),
     "xq_heads_nhwc_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int]),
     "xq_tower_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "xq_tower256_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_policy_fc_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "xq_value_head_bf16": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p]),
     "xq_replay_last_error": (C.c_char_p, []),

@@ -37,6 +37,7 @@
 #include "../../include/xq_selfplay.h"
 #include "../../include/xq_debug.h"
 #include "xq_mfma.hpp"
+#include "xq_tower_args.hpp"
 #include <atomic>
 #include <type_traits>
 #include <utility>
@@ -54,22 +55,7 @@ constexpr int WBUF_BYTES = COUT * 128;        // one weight stage: [128 cout][64
 constexpr int LDS_BYTES = 2 * ACT_BYTES + 2 * WBUF_BYTES + 256 + 2 * 512;
 constexpr int LDS_BYTES4 = 4 * ACT_BYTES + 2 * WBUF_BYTES + 256 + 2 * 512;      // k_tower16b<.., NB = 4>
 
-struct TowerArgs {
-    const uint16_t *planes;    // [G][90][16]
-    const uint16_t *w1;        // [9][128][16]
-    const uint16_t *wt;        // [2*nblocks][9][128][128]
-    const float *bias;         // [1 + 2*nblocks][128]
-    const uint16_t *wh;        // [64][128]  (rows 0..31 policy, 32..39 value, rest zero)
-    const float *bh;           // [64]
-    uint16_t *P;               // [G][90][32]
-    uint16_t *V;               // [G][90][8]
-    int G, nblocks;
-    unsigned long long *stamps;   // diagnostic builds only: 64 u64 per workgroup
-    // evaluator row compaction (xq_engine_set_row_compaction), both optional: board b reads the planes of row
-    // row_src[b] and only boards below *n_rows exist (device values of the preceding k_assign_rows)
-    const int32_t *row_src;
-    const int32_t *n_rows;
-};
+// (TowerArgs, the kernels' argument block, is shared with the 256-channel kernel: xq_tower_args.hpp)
 
 template <bool STAMP>
 __global__ __launch_bounds__(256, 2) void k_tower(TowerArgs A)
@@ -804,20 +790,7 @@ static void *clock_sample_for_this_device()
     return p;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remembered per (kernel, device
-// ordinal) - a process may drive several GPUs (xq_config.device) - in one atomic bit mask per kernel
-template <auto KERNEL>
-static int tower_lds_opt_in(int bytes)
-{
-    static std::atomic<uint64_t> done{ 0 };
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return XQ_E_HIP;
-    if (done.load(std::memory_order_acquire) >> dev & 1) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return XQ_E_HIP;
-    done.fetch_or(1ull << dev, std::memory_order_release);
-    return 0;
-}
+// (tower_lds_opt_in, the per-device opt-in to a kernel's dynamic LDS size: xq_tower_args.hpp)
 
 #include "xq_tower1wa.hpp"
 #if XQ_TOWER_PROBES

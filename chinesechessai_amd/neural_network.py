@@ -172,8 +172,9 @@ class InferenceNet(nn.Module):
             keeps the reference's 8,100 columns in order (padded to 8,256 on the hand-written path).  Callers that
             index logits by move must go through column_map (the engine does: xq_engine_set_logit_columns).
 
-    The hand-written kernels cover dtype=bfloat16, c_in=16 (channels-last), 128 channels on a CUDA device; any
-    other configuration raises ValueError unless allow_library_fallback=True asks for PyTorch's library kernels.
+    The hand-written kernels cover dtype=bfloat16, c_in=16 (channels-last), 128 or 256 channels on a CUDA device (256:
+    the single-launch trunk only, fused_tower=False raises); any other configuration raises ValueError unless
+    allow_library_fallback=True asks for PyTorch's library kernels.
     row_src / n_rows (device pointers from SelfPlayEngine.row_map(), hand-written fused path only): evaluator row
     compaction - row r reads the planes of x[row_src[r]], writes outputs to row r, rows >= *n_rows are skipped.
     """
@@ -203,14 +204,19 @@ class InferenceNet(nn.Module):
         self.cb = nn.ParameterList([nn.Parameter(b.to(device=device, dtype=dtype), requires_grad=False)
                                     for _, b in convs])
         # hand-written fused conv path: weights as [tap][cout][cin] bf16, bias fp32
+        self.channels = net.conv1.out_channels
         self.use_hip_conv = (dtype == torch.bfloat16 and c_in == 16 and str(device).startswith("cuda")
-                             and net.conv1.out_channels == 128)
+                             and self.channels in (128, 256))
         if not self.use_hip_conv and not allow_library_fallback:
-            # the hand-written kernels cover bf16, channels-last 16-plane input, 128 channels; anything else
+            # the hand-written kernels cover bf16, channels-last 16-plane input, 128 or 256 channels; anything else
             # would run on library kernels (MIOpen / hipBLASLt): only on request, never silently
-            raise ValueError("InferenceNet: no hand-written HIP path for dtype=%s, c_in=%d, channels=%d, device=%s; "
+            raise ValueError("InferenceNet: no hand-written HIP path for dtype=%s, c_in=%d, channels=%d, device=%s (the "
+                             "kernels cover bfloat16, c_in=16, 128 or 256 channels, cuda); "
                              "pass allow_library_fallback=True to run this configuration on PyTorch's library kernels "
-                             "(parity / debugging runs only)" % (dtype, c_in, net.conv1.out_channels, device))
+                             "(parity / debugging runs only)" % (dtype, c_in, self.channels, device))
+        if self.use_hip_conv and self.channels == 256 and not fused_tower:
+            raise ValueError("InferenceNet: 256 channels run on the single-launch trunk only (csrc/xq_tower256.hip); "
+                             "there is no per-layer 256-channel kernel, fused_tower=False is not available")
         self._buf = None
         self._hbuf = None
         self.tower_events = None
@@ -222,7 +228,7 @@ class InferenceNet(nn.Module):
             self.hip_b = [b.to(device=device, dtype=torch.float32).contiguous() for _, b in convs]
             # the same tensors as one weight stream / one bias table for the single-launch trunk
             self.hip_wt = (torch.stack(self.hip_w[1:]).contiguous() if self.n_blocks else
-                           torch.zeros((0, 9, 128, 128), dtype=dtype, device=device))
+                           torch.zeros((0, 9, self.channels, self.channels), dtype=dtype, device=device))
             self.hip_bt = torch.stack(self.hip_b).contiguous()
         # heads: the two 1x1 convolutions share one GEMM (32 + 8 output channels)
         pw, pb = _fold_bn(net.policy_conv, net.policy_bn)
@@ -325,7 +331,8 @@ class InferenceNet(nn.Module):
 
     def trunk_hip(self, x, row_src=None, n_rows=None):
         """planes -> (policy-head activations [G, 2880], value-head activations [G, 720]) in one
-        launch of k_tower: activations stay in LDS across all layers."""
+        launch of the trunk kernel of the network's width (xq_tower_nhwc_bf16: 128 channels, xq_tower256_nhwc_bf16:
+        256): activations stay in LDS across all layers."""
         from . import _lib
         g = x.shape[0]
         xin = x.permute(0, 2, 3, 1)
@@ -335,10 +342,12 @@ class InferenceNet(nn.Module):
         if self.tower_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        _lib.check(_lib.lib().xq_tower_nhwc_bf16(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
-                                                 self.hip_w[0].data_ptr(), self.hip_wt.data_ptr(), self.hip_bt.data_ptr(),
-                                                 self.hip_hw.data_ptr(), self.hip_hb.data_ptr(), hp.data_ptr(),
-                                                 hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
+        L = _lib.lib()
+        tower = L.xq_tower256_nhwc_bf16 if self.channels == 256 else L.xq_tower_nhwc_bf16
+        _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
+                         self.hip_w[0].data_ptr(), self.hip_wt.data_ptr(), self.hip_bt.data_ptr(),
+                         self.hip_hw.data_ptr(), self.hip_hb.data_ptr(), hp.data_ptr(),
+                         hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
         if ev is not None:
             ev[1].record()
             self.tower_events.append(ev)

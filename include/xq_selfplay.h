@@ -468,6 +468,17 @@ int  xq_tower_nhwc_bf16(void *hip_stream, const void *planes_dev, const void *w1
                         const void *bias_dev, const void *wh_dev, const void *bh_dev, void *policy_out_dev,
                         void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev, const void *n_rows_dev);
 
+/* The same trunk for a 256-channel network (neural_network.py:47-71,172-187, BN folded), one launch of its own kernel
+ * (csrc/xq_tower256.hip): conv3x3(16->256)+ReLU, n_blocks residual blocks, both 1x1 heads + ReLU; activations never
+ * leave LDS between layers.  planes [n][10][9][16] bf16, w1 [9][256][16] bf16, wt [2*n_blocks][9][256][256] bf16, bias
+ * float32 [1 + 2*n_blocks][256] (conv1 first), wh [64][256] bf16 (rows 0..31 policy, 32..39 value, rest zero), bh
+ * float32[64]; outputs, arithmetic (bf16 storage between layers, fp32 accumulation in one fixed order per element, the
+ * skip added in fp32 before a block's single rounding), argument checks, return codes and row_src_dev / n_rows_dev as
+ * xq_tower_nhwc_bf16. */
+int  xq_tower256_nhwc_bf16(void *hip_stream, const void *planes_dev, const void *w1_dev, const void *wt_dev,
+                           const void *bias_dev, const void *wh_dev, const void *bh_dev, void *policy_out_dev,
+                           void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev, const void *n_rows_dev);
+
 /* The policy head's fully-connected layer (neural_network.py:39,64: nn.Linear(32*10*9, 8100) applied to the
  * flattened policy-conv activations): logits[m][n] = bias[n] + sum_k act[m][k] * w[n][k].
  * act [n_rows][k] bf16 (the (h, w, c)-ordered output of xq_tower_nhwc_bf16 / xq_heads_nhwc_bf16), w [n_cols][k]
