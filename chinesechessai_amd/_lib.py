@@ -13,9 +13,10 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libxq_hip.so")
 SOURCES = [os.path.join(CSRC, "xq_engine.hip"), os.path.join(CSRC, "xq_conv.hip"), os.path.join(CSRC, "xq_replay.hip"),
            os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip"), os.path.join(CSRC, "xq_policy_loss.hip"),
-           os.path.join(CSRC, "xq_tower256.hip")]
-# per-source flags: the 256-channel trunk is compiled without packed fp32 arithmetic (it has no use for it)
-SOURCE_FLAGS = {"xq_tower256.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+           os.path.join(CSRC, "xq_tower256.hip"), os.path.join(CSRC, "xq_tower_mx.hip")]
+# per-source flags: the 256-channel and the MXFP8 trunk are compiled without packed fp32 arithmetic (they have no use for it)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+SOURCE_FLAGS = {"xq_tower256.hip": _NO_PK_F32, "xq_tower_mx.hip": _NO_PK_F32}
 HEADERS = [os.path.join(CSRC, "xq_device.hpp"), os.path.join(CSRC, "xq_attack.hpp"), os.path.join(CSRC, "xq_mfma.hpp"), os.path.join(CSRC, "xq_tower_args.hpp"), os.path.join(CSRC, "xq_tower_probes.hpp"),
            os.path.join(CSRC, "xq_tower1wa.hpp"), os.path.join(CSRC, "xq_tower1wa_body.inc"), os.path.join(CSRC, "xq_policy_fc1w_body.inc"),
            os.path.join(_HERE, "..", "include", "xq_selfplay.h"), os.path.join(_HERE, "..", "include", "xq_debug.h")]
@@ -201,6 +202,7 @@ _SIGNATURES = {
     "xq_heads_nhwc_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int]),
     "xq_tower_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_tower256_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "xq_tower_mxfp8_nhwc": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_policy_fc_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "xq_value_head_bf16": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p]),
     "xq_replay_last_error": (C.c_char_p, []),

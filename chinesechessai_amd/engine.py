@@ -171,7 +171,7 @@ class TorchNetEvaluator:
     deterministic = True
 
     def __init__(self, net, dtype=None, channels_last=True, chunk=None, policy_columns="reachable", fused_tower=True,
-                 leaf_dedupe=True, eval_cache=True):
+                 leaf_dedupe=True, eval_cache=True, trunk="bf16"):
         import torch
         from .neural_network import InferenceNet
         self.torch = torch
@@ -187,9 +187,11 @@ class TorchNetEvaluator:
         self.channels_last = channels_last
         # bf16 channels-last = the hand-written kernels; float32 (or NCHW) = PyTorch's library kernels, asked
         # for explicitly by choosing that dtype / layout (parity runs against the fp32 reference)
+        if isinstance(net, InferenceNet) and net.trunk != trunk:
+            raise ValueError("TorchNetEvaluator: trunk=%r, but the InferenceNet handed in was built with trunk=%r" % (trunk, net.trunk))
         self.inet = net if isinstance(net, InferenceNet) else InferenceNet(
             net, dtype=dtype, c_in=16 if channels_last else 15, device="cuda", policy_columns=policy_columns,
-            fused_tower=fused_tower, allow_library_fallback=(dtype != torch.bfloat16 or not channels_last))
+            fused_tower=fused_tower, allow_library_fallback=(dtype != torch.bfloat16 or not channels_last), trunk=trunk)
         self.chunk = chunk
         self.kind = _lib.EVAL_LOGITS_BF16 if dtype == torch.bfloat16 else _lib.EVAL_LOGITS_F32
         self.row_compaction = bool(self.inet.supports_row_map and not chunk)

@@ -161,6 +161,35 @@ def _fold_bn(conv, bn):
     return w, b
 
 
+def mx_quantize(t):
+    """OCP MXFP8 along the last axis (a multiple of 32): per block of 32 consecutive values m = the largest magnitude,
+    e = floor(log2 m) - 8, + 1 if m * 2^-e > 448 (nothing saturates), scale byte = e + 127 clamped to 0..254 (127 for an
+    all-zero block), elements x * 2^(127 - byte) rounded to nearest-even e4m3.  Returns (uint8 e4m3 bytes of t's shape,
+    uint8 E8M0 scale bytes [..., n / 32]).  Plain torch, any device; the rule csrc/xq_tower_mx.hip applies to its
+    activations and the one InferenceNet(trunk="mxfp8") applies to the tower weights."""
+    x = t.detach().to(torch.float64)
+    assert x.shape[-1] % 32 == 0 and bool(torch.isfinite(x).all())
+    xb = x.reshape(x.shape[:-1] + (x.shape[-1] // 32, 32))
+    m = xb.abs().amax(-1)
+    e = torch.frexp(m)[1].to(torch.int64) - 9                        # m = f * 2^ex, f in [0.5, 1): floor(log2 m) = ex - 1
+    e = e + (torch.ldexp(m, -e) > 448).to(torch.int64)
+    byte = torch.where(m == 0, torch.full_like(e, 127), (e + 127).clamp(0, 254))
+    y = torch.ldexp(xb, (127 - byte).unsqueeze(-1))
+    assert y.numel() == 0 or float(y.abs().max()) <= 448.0            # float8_e4m3fn's conversion turns 480 into NaN, not 448
+    # nearest-even on the e4m3 grid in float64 (spacing 2^(floor(log2 |y|) - 3), 2^-9 below 2^-6): one rounding,
+    # whatever the input type; the conversion below is then exact
+    step = torch.ldexp(torch.ones_like(y), (torch.frexp(y)[1].to(torch.int64) - 1).clamp(min=-6) - 3)
+    q = (torch.round(y / step) * step).to(torch.float32).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8).reshape(t.shape), byte.to(torch.uint8)
+
+
+def mx_dequantize(q, scale):
+    """The float64 values of mx_quantize's (e4m3 bytes, scale bytes)."""
+    v = q.view(torch.float8_e4m3fn).to(torch.float32).to(torch.float64)
+    v = v.reshape(v.shape[:-1] + (v.shape[-1] // 32, 32))
+    return torch.ldexp(v, (scale.to(torch.int64) - 127).unsqueeze(-1)).reshape(q.shape)
+
+
 class InferenceNet(nn.Module):
     """Folded, channels-last, low-precision forward of a ChessNet for the engine.
 
@@ -180,8 +209,19 @@ class InferenceNet(nn.Module):
     """
 
     def __init__(self, net, dtype=torch.bfloat16, c_in=16, device="cuda", policy_columns="reachable", fused_tower=True,
-                 allow_library_fallback=False):
+                 allow_library_fallback=False, trunk="bf16"):
         super().__init__()
+        if trunk not in ("bf16", "mxfp8"):
+            raise ValueError("trunk must be 'bf16' or 'mxfp8'")
+        # "mxfp8" (opt-in): the 2 * n_blocks tower convolutions of a 128-channel network on the block-scaled fp8 matrix
+        # pipe (csrc/xq_tower_mx.hip: e4m3 x e4m3, fp32 accumulation, the residual stream stays bf16); input convolution,
+        # heads and everything behind them as with "bf16"
+        if trunk == "mxfp8" and not (net.conv1.out_channels == 128 and dtype == torch.bfloat16 and c_in == 16
+                                     and str(device).startswith("cuda") and fused_tower):
+            raise ValueError("InferenceNet: trunk='mxfp8' is the single-launch kernel of csrc/xq_tower_mx.hip: 128 channels, "
+                             "bfloat16, c_in=16, cuda and fused_tower=True (got channels=%d, dtype=%s, c_in=%d, device=%s, "
+                             "fused_tower=%s)" % (net.conv1.out_channels, dtype, c_in, device, fused_tower))
+        self.trunk = trunk
         self.dtype = dtype
         self.fused_tower = fused_tower                 # one launch for the whole trunk (csrc/xq_tower.hip)
         self.c_in = c_in
@@ -230,6 +270,15 @@ class InferenceNet(nn.Module):
             self.hip_wt = (torch.stack(self.hip_w[1:]).contiguous() if self.n_blocks else
                            torch.zeros((0, 9, self.channels, self.channels), dtype=dtype, device=device))
             self.hip_bt = torch.stack(self.hip_b).contiguous()
+        if trunk == "mxfp8":
+            # the folded float64 tower weights as [layer][tap][cout][cin], quantised along cin in blocks of 32
+            wt64 = (torch.stack([w.permute(2, 3, 0, 1).reshape(9, 128, 128) for w, _ in convs[1:]]) if self.n_blocks else
+                    torch.zeros((0, 9, 128, 128), dtype=torch.float64))
+            wq, ws = mx_quantize(wt64.cpu())
+            self.hip_wq, self.hip_ws = wq.to(device).contiguous(), ws.to(device).contiguous()
+            # nothing reads the bf16 tower weights on this path: neither uploaded nor part of the rank digest
+            self.hip_w = self.hip_w[:1]
+            self.hip_wt = torch.zeros((0, 9, 128, 128), dtype=dtype, device=device)
         # heads: the two 1x1 convolutions share one GEMM (32 + 8 output channels)
         pw, pb = _fold_bn(net.policy_conv, net.policy_bn)
         vw, vb = _fold_bn(net.value_conv, net.value_bn)
@@ -290,7 +339,8 @@ class InferenceNet(nn.Module):
         if not self.use_hip_conv:
             return [p.data for p in self.parameters()]
         return [self.hip_w[0], self.hip_wt, self.hip_bt, self.hip_hw, self.hip_hb, self.pfw.data, self.hip_pfb,
-                self.hip_v1w, self.hip_v1b, self.hip_v2w, self.hip_v2b]
+                self.hip_v1w, self.hip_v1b, self.hip_v2w, self.hip_v2b] + (
+                    [self.hip_wq, self.hip_ws] if self.trunk == "mxfp8" else [])
 
     def _tower_hip(self, x):
         """Residual tower on the hand-written fused conv kernel (csrc/xq_conv.hip): one launch per
@@ -343,11 +393,17 @@ class InferenceNet(nn.Module):
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         L = _lib.lib()
-        tower = L.xq_tower256_nhwc_bf16 if self.channels == 256 else L.xq_tower_nhwc_bf16
-        _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
-                         self.hip_w[0].data_ptr(), self.hip_wt.data_ptr(), self.hip_bt.data_ptr(),
-                         self.hip_hw.data_ptr(), self.hip_hb.data_ptr(), hp.data_ptr(),
-                         hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
+        if self.trunk == "mxfp8":
+            _lib.check(L.xq_tower_mxfp8_nhwc(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
+                                             self.hip_w[0].data_ptr(), self.hip_wq.data_ptr(), self.hip_ws.data_ptr(),
+                                             self.hip_bt.data_ptr(), self.hip_hw.data_ptr(), self.hip_hb.data_ptr(),
+                                             hp.data_ptr(), hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
+        else:
+            tower = L.xq_tower256_nhwc_bf16 if self.channels == 256 else L.xq_tower_nhwc_bf16
+            _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
+                             self.hip_w[0].data_ptr(), self.hip_wt.data_ptr(), self.hip_bt.data_ptr(),
+                             self.hip_hw.data_ptr(), self.hip_hb.data_ptr(), hp.data_ptr(),
+                             hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
         if ev is not None:
             ev[1].record()
             self.tower_events.append(ev)

@@ -479,6 +479,22 @@ int  xq_tower256_nhwc_bf16(void *hip_stream, const void *planes_dev, const void 
                            const void *bias_dev, const void *wh_dev, const void *bh_dev, void *policy_out_dev,
                            void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev, const void *n_rows_dev);
 
+/* The 128-channel trunk with its 2 * n_blocks tower convolutions in MXFP8 (csrc/xq_tower_mx.hip), one launch.  The
+ * arguments of xq_tower_nhwc_bf16 with wt replaced by wq_dev, the OCP e4m3 bytes [2*n_blocks][9][128][128]
+ * ([layer][tap][cout][cin]), and wscale_dev, the E8M0 scale bytes [2*n_blocks][9][128][4] (one per 32 consecutive
+ * cin; weight = e4m3 * 2^(byte - 127)).  Input convolution and heads run in bf16 on w1 / wh as in xq_tower_nhwc_bf16;
+ * the tower convolutions multiply e4m3 by e4m3 with fp32 accumulation and fp32 bias.  Every layer output is rounded to
+ * bf16 once (the skip added in fp32 before that) and the residual stream keeps the bf16 value; the next convolution's
+ * operand is that value quantised per pixel and block of 32 consecutive channels: m = the block's largest magnitude,
+ * e = floor(log2 m) - 8, + 1 if m * 2^-e > 448, scale byte e + 127 clamped to 0..254 (127 for an all-zero block),
+ * elements x * 2^(127 - byte) rounded to nearest-even e4m3.  One fixed accumulation order per output element:
+ * results do not depend on the launch, the row or n_boards.  Argument checks, return codes, outputs and row_src_dev /
+ * n_rows_dev as xq_tower_nhwc_bf16. */
+int  xq_tower_mxfp8_nhwc(void *hip_stream, const void *planes_dev, const void *w1_dev, const void *wq_dev,
+                         const void *wscale_dev, const void *bias_dev, const void *wh_dev, const void *bh_dev,
+                         void *policy_out_dev, void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev,
+                         const void *n_rows_dev);
+
 /* The policy head's fully-connected layer (neural_network.py:39,64: nn.Linear(32*10*9, 8100) applied to the
  * flattened policy-conv activations): logits[m][n] = bias[n] + sum_k act[m][k] * w[n][k].
  * act [n_rows][k] bf16 (the (h, w, c)-ordered output of xq_tower_nhwc_bf16 / xq_heads_nhwc_bf16), w [n_cols][k]
