@@ -15,12 +15,14 @@
 //                   with its network planes                              self_play.py:103-148
 //   k_hashnet       exact dyadic evaluator for parity tests              SURVEY.md Appendix B
 //   k_end_search    consume the last round                               self_play.py:146-154
+//                   (xq_engine_set_last_round_visits_only: a ply's last round parks nothing - its leaf's
+//                   visits are booked along the path at once, no network row, nothing left to consume)
 //   k_play_move     visits -> pi -> np.random.choice -> make_move        self_play.py:219-256
 //   k_finalize      z table                                              self_play.py:259-310
 //   k_rules_*       batch entry points on caller boards (host mirror of ChineseChess)
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (float results are part of the
-// parity contract: PUCT is float32 stepwise, W is float64, rewards/z are float64).
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, packed fp32 arithmetic off (float results
+// are part of the parity contract: PUCT is float32 stepwise, W is float64, rewards/z are float64).
 #include "xq_device.hpp"
 #include "../../include/xq_selfplay.h"
 #include "../../include/xq_debug.h"
@@ -151,6 +153,9 @@ struct Eng {
     uint64_t cap_seed;
     uint32_t cap_thresh;      // round(full_prob * 2^24): a ply is full iff the top 24 bits of its hash lie below
     int cap_fast, cap_record_fast;
+    // ---- xq_engine_set_last_round_visits_only (opt-in, result-identical elimination).  Read by the host alone: it picks
+    // the LRV build of the round for the launches that can meet a slot's last round; no kernel loads it.
+    int last_visits_only;
 };
 
 // the evaluator outputs a tree kernel consumes, one per network (single-network launches: twice the same)
@@ -1030,7 +1035,17 @@ __device__ __forceinline__ int pick_child(int v0, int v1, int c)
 //   every other launch runs holds none of its code - no load, no branch, no register (with the switch as a run-time
 //   flag in the one build: 127 -> 140 spilled SGPRs in the flagship kernel; 20 B of scratch with the budget held in a
 //   register across the round).
-template <bool STAMP, bool CAP>
+//   LRV: the last-round-visits-only build (xq_engine_set_last_round_visits_only), launched only while that switch is on and
+//   only for rounds that can be some slot's last one; the other builds hold none of its code.  A slot is in its LAST round
+//   when this round uses up its ply's budget and the ply has more than one round.  Whatever the evaluator would say about
+//   the leaf of that round reaches no output: k_end_search would expand the leaf (children nobody visits: no selection
+//   follows the last backup), add mult * v to W along the path (k_play_move reads N, never W) and mult to N.  So the round
+//   descends and generates the leaf's moves as always - a terminal leaf backs up by the rules and moves the round's next
+//   simulation - and for a non-terminal leaf books the remaining simulations as visits along the path and parks nothing:
+//   no planes, no dedupe or cache traffic, no leaf_* store, leaf_node stays LEAF_NONE (phase A's consume left it so), and
+//   k_hashnet / k_assign_rows / k_end_search skip the slot as they skip a round of terminal leaves.  The root branch
+//   (record_leaf) is untouched: a one-round ply parks its root as it always did.
+template <bool STAMP, bool CAP, bool LRV = false>
 __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_count, const EvalPair &ev,
                                  void *planes, int fmt, unsigned long long *stamps)
 {
@@ -1082,6 +1097,12 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
     if constexpr (CAP) {
         const int left = uni(sims_v) - round * E.leaf_batch;
         batch_count = left < 0 ? 0 : (left > E.leaf_batch ? E.leaf_batch : left);
+    }
+    // this round uses up the slot's budget and is not the ply's only one (wave-uniform; LRV build only)
+    bool last = false;
+    if constexpr (LRV) {
+        if constexpr (CAP) last = uni(sims_v) > E.leaf_batch && uni(sims_v) - round * E.leaf_batch <= E.leaf_batch;
+        else last = round == E.nrounds - 1 && E.nrounds > 1;
     }
     if (round == 0) p_node = LEAF_NONE;
     if (gs.done) return;
@@ -1360,6 +1381,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
             unsigned long long ec_first = 0ull;
             DedupeLook look{ 0u, 0ull };
             auto early = [&](const int8_t *bd) {
+                if constexpr (LRV) { if (last) return; }     // a leaf that will not be parked: nothing leaves early
                 my_dword = lane < 12 ? pack_dword(bd, lane) : 0u;
                 if (E.dedupe || E.ec_on) h = position_hash(my_dword, leaf_side, net);
                 if (E.ec_on) ec_first = ec_ld64(&E.ec_state[eval_cache_pos(E, h)]);
@@ -1376,6 +1398,19 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
             flags |= mr.is_check ? F_CHECK : 0;
             XQ_STAMP(7);
             const bool terminal = (mr.n_legal == 0) || (st.winner != WINNER_NONE);     // self_play.py:126
+            if constexpr (LRV) {
+                if (!terminal && last) {
+                    // the slot's last round: the remaining simulations all end at this leaf - book them as visits (what
+                    // k_end_search's backup would add to N; nobody reads W or the leaf's children any more) and park nothing
+                    if (lane == 0) T.fl[node] = (uint8_t)flags;
+                    for (int l = lane; l <= depth; l += 64) {
+                        const int x = l == 0 ? root : L.path_node[l - 1];
+                        T.N[x] += (uint32_t)sims_left;
+                    }
+                    mem_fence_wave();
+                    return;
+                }
+            }
             if (!terminal) {
                 if (lane == 0) {
                     T.fl[node] = (uint8_t)flags;
@@ -1410,7 +1445,7 @@ __device__ void search_round_one(const Eng &E, WaveLds &L, int round, int batch_
 }
 
 // OCC = minimum waves per SIMD requested from the register allocator.
-template <int OCC, bool VL, bool STAMP = false, bool CAP = false>
+template <int OCC, bool VL, bool STAMP = false, bool CAP = false, bool LRV = false>
 __global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int batch_count, EvalPair ev, void *planes, int fmt,
                                                           unsigned long long *stamps = nullptr)
 {
@@ -1419,7 +1454,7 @@ __global__ __launch_bounds__(64, OCC) void k_search_round(Eng E, int round, int 
     // slowest game)
     __shared__ WaveLds L;
     if constexpr (VL) search_round_generic<true>(E, L, round, batch_count, ev, planes, fmt);
-    else search_round_one<STAMP, CAP>(E, L, round, batch_count, ev, planes, fmt, stamps);
+    else search_round_one<STAMP, CAP, LRV>(E, L, round, batch_count, ev, planes, fmt, stamps);
 }
 
 __constant__ uint32_t c_crc_table[256];
@@ -1719,6 +1754,9 @@ __global__ __launch_bounds__(64) void k_play_move(Eng E)
         const float p0 = j0 < n ? T.P[fc + j0] : 0.f, p1 = j1 < n ? T.P[fc + j1] : 0.f;
         // (the child's move list is the legal-move list the leaf's make_move produced: it must equal this one)
         const bool same = (j0 >= n || m0 == L.legal[j0]) && (j1 >= n || m1 == L.legal[j1]);
+        // (a child that was never expanded has nc == 0 from its edge's initialisation - also the leaf of a last round under
+        // xq_engine_set_last_round_visits_only, which has visits but no expansion: ok is false, roots_not_ready counts the
+        // game and the next ply's round 0 evaluates the root, as on a game's first ply)
         const bool ok = n != 0 && n == mr.n_legal && __all(same) && pair_v == 0;
         wave_sync();
         if (ok) {
@@ -2484,6 +2522,7 @@ extern "C" int xq_engine_set_tree_reuse(xq_engine *e, int enable)
     Eng &E = e->E;
     if (enable && E.eval_carry) return fail(XQ_E_INVALID, "tree reuse cannot be combined with root evaluation carry-over");
     if (enable && E.cap_fast) return fail(XQ_E_INVALID, "tree reuse cannot be combined with the playout cap (a kept subtree carries another ply's budget): xq_engine_set_playout_cap(e, 1, 0, 0, 0) first");
+    if (enable && E.last_visits_only) return fail(XQ_E_INVALID, "tree reuse cannot be combined with last-round visits only (a kept subtree keeps W and the last leaf's expansion): xq_engine_set_last_round_visits_only(e, 0) first");
     E.tree_reuse = enable ? 1 : 0;
     E.want_check = (enable || E.nrounds >= 12) ? 1 : 0;      // (a kept subtree's paths reach 12 plies with any number of rounds)
     if (int rc = grow_nodes(e)) return rc;
@@ -2507,6 +2546,7 @@ extern "C" int xq_engine_set_virtual_loss(xq_engine *e, int enable)
     if (K > 64) return fail(XQ_E_INVALID, "virtual loss needs leaf_batch <= 64 (one lane per pending slot)");
     if (enable && E.eval_carry) return fail(XQ_E_INVALID, "virtual loss cannot be combined with root evaluation carry-over");
     if (enable && E.cap_fast) return fail(XQ_E_INVALID, "virtual loss cannot be combined with the playout cap (its search round takes the count by value): xq_engine_set_playout_cap(e, 1, 0, 0, 0) first");
+    if (enable && E.last_visits_only) return fail(XQ_E_INVALID, "virtual loss cannot be combined with last-round visits only (its search round parks every leaf): xq_engine_set_last_round_visits_only(e, 0) first");
     HIPCHK(hipSetDevice(e->cfg.device));
     if (K != E.leaf_slots) {
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -2703,15 +2743,32 @@ static int search_round_impl(xq_engine *e, int round, int eval_kind, const void 
     }
 #define XQ_LAUNCH_SEARCH(OCC, VLB) hipLaunchKernelGGL((k_search_round<OCC, VLB>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, \
                                                     round, batch, evp, planes, fmt, (unsigned long long *)nullptr)
+    // last round visits only: its builds run only where a slot can be in its last round - round nrounds - 1 of a ply of
+    // more than one round, or any round past 0 under the playout cap (a fast ply ends early); every other launch is the
+    // build it always was
+    const bool lrv = e->E.last_visits_only && !e->E.vloss && round > 0 && (e->E.cap_fast || round == e->E.nrounds - 1);
     if (e->E.vloss) XQ_LAUNCH_SEARCH(4, true);
-    else if (e->E.cap_fast)              // the playout-cap build: the round's count comes from ply_sims[g], not from `batch`
-        hipLaunchKernelGGL((k_search_round<4, false, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
-                           planes, fmt, (unsigned long long *)nullptr);
+    else if (e->E.cap_fast) {            // the playout-cap build: the round's count comes from ply_sims[g], not from `batch`
+        if (lrv)
+            hipLaunchKernelGGL((k_search_round<4, false, false, true, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch,
+                               evp, planes, fmt, (unsigned long long *)nullptr);
+        else
+            hipLaunchKernelGGL((k_search_round<4, false, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
+                               planes, fmt, (unsigned long long *)nullptr);
+    }
 #if XQ_TOWER_PROBES
-    else if (g_search_stamps)
-        hipLaunchKernelGGL((k_search_round<4, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
-                           planes, fmt, (unsigned long long *)g_search_stamps);
+    else if (g_search_stamps) {
+        if (lrv)
+            hipLaunchKernelGGL((k_search_round<4, false, true, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch,
+                               evp, planes, fmt, (unsigned long long *)g_search_stamps);
+        else
+            hipLaunchKernelGGL((k_search_round<4, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
+                               planes, fmt, (unsigned long long *)g_search_stamps);
+    }
 #endif
+    else if (lrv)
+        hipLaunchKernelGGL((k_search_round<4, false, false, false, true>), dim3(e->E.G), dim3(64), 0, e->stream, e->E, round, batch, evp,
+                           planes, fmt, (unsigned long long *)nullptr);
     else switch (g_search_occ) {
 #if XQ_TOWER_PROBES                 // the other register budgets spill 27-58 VGPRs: comparison builds, probes library only
     case 3: XQ_LAUNCH_SEARCH(3, false); break;
@@ -2984,6 +3041,30 @@ extern "C" int xq_engine_set_root_eval_carry(xq_engine *e, int enable)
         if (dalloc(e, E.root_ready, (size_t)E.G) || dalloc(e, E.roots_not_ready, (size_t)1)) return fail(XQ_E_HIP, "hipMalloc failed");
     }
     E.eval_carry = enable ? 1 : 0;
+    return 0;
+}
+
+// Opt-in, result-identical work elimination (default off; no counterpart in the reference, which evaluates the leaf of
+// every round, self_play.py:137-148): a ply's LAST search round evaluates nothing.  What the evaluator says about that
+// round's leaf reaches no output - the leaf's children are never visited (no selection follows the last backup), W is
+// never read again (xq_engine_play_move reads the root's children's N, and for the carry-over the played child's own
+// expansion) - so the round books the leaf's remaining simulations as visits along its path and parks no leaf: no
+// planes, no network row, nothing for xq_engine_end_search to consume.  Terminal leaves are handled as always.  The one
+// reader of the last leaf's priors is the carry-over when that very leaf is played: an unexpanded child is "not ready",
+// so the next ply's round 0 evaluates it, as on a game's first ply (xq_engine_roots_not_ready counts it).  A ply of one
+// round (sims <= leaf_batch) is left alone.  The tree after a bare search differs from the reference's in value_sum
+// and in the last leaf's children, which is why this is a switch; visit counts and moves do not differ.  Valid with root
+// noise, two-network rounds, the playout cap, with or without the carry-over and the cache (whose table then misses the
+// last rounds' positions: fewer fills, never another answer).  Not combinable with tree reuse (a kept subtree keeps W
+// and the leaf's expansion) or virtual loss (its round is another kernel).
+extern "C" int xq_engine_set_last_round_visits_only(xq_engine *e, int enable)
+{
+    if (!e) return fail(XQ_E_INVALID, "null engine");
+    Eng &E = e->E;
+    if (enable && (E.tree_reuse || E.vloss))
+        return fail(XQ_E_INVALID, "last-round visits only cannot be combined with tree reuse (a kept subtree keeps W and the last "
+                                  "leaf's expansion) or virtual loss (its search round parks every leaf)");
+    E.last_visits_only = enable ? 1 : 0;
     return 0;
 }
 

@@ -351,6 +351,9 @@ class SelfPlayEngine:
         self._noise = self._vloss = False
         self.tree_reuse = False
         self.playout_cap = None                                 # set_playout_cap: (full_prob, fast_sims, seed, record_fast)
+        # last round visits only: None = automatic (see set_last_round_visits_only), True / False = the caller's choice
+        self.last_round_visits_only = None
+        self._lrv_on = False
         if stream is not None:
             _lib.check(self.L.xq_engine_set_stream(h, C.c_void_p(stream)))
         if temperature >= 0.01 and temperature != 1.0:
@@ -438,6 +441,49 @@ class SelfPlayEngine:
         if self._carry_on and self.root_eval_carry is None:
             _lib.check(self.L.xq_engine_set_root_eval_carry(self.h, 0))
             self._carry_on = False
+
+    def set_last_round_visits_only(self, enable=None):
+        """Result-identical work elimination (xq_engine_set_last_round_visits_only): the last search round of a ply parks no
+        leaf and costs no evaluator row - what the network would say about that leaf reaches no output (nothing is selected
+        after the last backup, the move choice reads visit counts only), so the round books the leaf's visits along its path
+        and that is all.  Games, visit counts, pi and z do not change; the tree read back after a search does (value sums,
+        the last leaf's children), so a bare search() never gets it by itself.  True / False fix the choice (True raises
+        together with tree reuse or virtual loss), None is automatic: play() switches it on for lock-step games of ONE
+        evaluator that runs with row compaction and asks for the other eliminations too (leaf dedupe and evaluation cache:
+        TorchNetEvaluator at its defaults), while the carry-over is left to its own automatic rule and no extension is on
+        (no root noise, virtual loss, tree reuse, arena mode, playout cap, per-slot reuse) - what bench.py runs.
+        Everywhere else - play_refill(), a second network, a capped session, an explicit set_root_eval_carry(), an evaluator
+        that switches the dedupe or the cache off (it is counting rows), an evaluator without compaction (whose carried
+        roots are found by a roots_not_ready() read that would now rarely be 0) - it is on only by this call.  The evaluator is still called after every round: with compaction the forward after a last
+        round has no rows."""
+        if enable is None:
+            self.last_round_visits_only = None
+            return
+        _lib.check(self.L.xq_engine_set_last_round_visits_only(self.h, 1 if enable else 0))
+        self.last_round_visits_only = self._lrv_on = bool(enable)
+
+    def _auto_last_round(self, evaluator, opponent_evaluator):
+        """Decide the last-round elimination for the lock-step games about to start (play), after _auto_carry."""
+        if self.last_round_visits_only is not None:
+            return self._lrv_on
+        want = bool(opponent_evaluator is None and getattr(evaluator, "row_compaction", False)
+                    and getattr(evaluator, "leaf_dedupe", False) and getattr(evaluator, "eval_cache", False)
+                    and getattr(evaluator, "deterministic", False) and self.root_eval_carry is None and self._carry_on
+                    and not self.opponent_mode and not self._noise and not self._vloss and not self.tree_reuse
+                    and not self.playout_cap and not self._slot_reuse)
+        self._set_auto_last_round(want)
+        return want
+
+    def _set_auto_last_round(self, want):
+        if want != self._lrv_on:
+            _lib.check(self.L.xq_engine_set_last_round_visits_only(self.h, 1 if want else 0))
+            self._lrv_on = want
+
+    def _drop_auto_last_round(self):
+        # an extension is being switched on, or a driver that never asked for it starts: the automatic choice steps aside
+        # (an explicit one refuses in C where it must)
+        if self._lrv_on and self.last_round_visits_only is None:
+            self._set_auto_last_round(False)
 
     def set_row_compaction(self, enable=True):
         """Only slots with a pending leaf become evaluator rows (xq_engine_set_row_compaction); evaluators whose
@@ -637,6 +683,7 @@ class SelfPlayEngine:
         fresh tree every ply).  Call before new games are started."""
         if enable:
             self._drop_auto_carry()
+            self._drop_auto_last_round()
         _lib.check(self.L.xq_engine_set_tree_reuse(self.h, 1 if enable else 0))
         self.tree_reuse = bool(enable)
         self.set_temperature(self.temperature)             # counts ** (1/T) table must cover carried visits
@@ -648,6 +695,7 @@ class SelfPlayEngine:
         evaluator is bound."""
         if enable:
             self._drop_auto_carry()
+            self._drop_auto_last_round()
         _lib.check(self.L.xq_engine_set_virtual_loss(self.h, 1 if enable else 0))
         self._vloss = bool(enable)
         self.n_rows = self.n_games * self.L.xq_engine_leaf_slots(self.h)
@@ -735,6 +783,7 @@ class SelfPlayEngine:
         if self.playout_cap and opponent_evaluator is not None:
             raise _lib.XqError("the playout cap cannot be combined with a second network (evaluation games are not capped)")
         carry = self._auto_carry(evaluator, opponent_evaluator)
+        self._auto_last_round(evaluator, opponent_evaluator)
         self._bind(evaluator, opponent_evaluator)
         self.new_games(seeds)
         if uniforms is not None:
@@ -759,6 +808,7 @@ class SelfPlayEngine:
                     break
                 self.active_games_post()
         _lib.check(self.L.xq_engine_finalize(self.h))
+        self._drop_auto_last_round()          # (the automatic choice holds for these games only: a bare search() keeps the reference's tree)
         for ev in (evaluator, opponent_evaluator):
             if ev is not None and hasattr(ev, "after_play"):
                 ev.after_play(self)
@@ -795,6 +845,7 @@ class SelfPlayEngine:
         if reuse or self._slot_reuse:        # (a session that never asked for it makes no call)
             self.set_per_slot_reuse(reuse, keep_plies=(self.reuse_keep_plies or (3 if pairing.any() else 2)) if reuse else 2)
         carry = self._auto_carry(evaluator, opponent_evaluator, reuse=reuse)
+        self._drop_auto_last_round()          # (refill sessions get the last-round elimination by set_last_round_visits_only(True) only)
         self._bind(evaluator, opponent_evaluator, per_slot=two)
         _lib.check(self.L.xq_engine_refill_begin2(self.h, _lib.ptr(seeds), total, _lib.ptr(pairing)))
         active = np.zeros(1, np.int32)

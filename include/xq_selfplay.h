@@ -279,6 +279,20 @@ int  xq_engine_pack_samples(xq_engine *e, void *records_dev /* xq_sample_record[
 int  xq_engine_set_root_eval_carry(xq_engine *e, int enable);
 int  xq_engine_roots_not_ready(xq_engine *e, int32_t *n_host);
 
+/* Opt-in, result-identical work elimination (off until asked for): the LAST search round of a ply of more than one
+ * round evaluates nothing.  The evaluator's answer for that round's leaf reaches no output - no selection follows the
+ * last backup, so the leaf's children are never visited, and xq_engine_play_move reads visit counts, never value sums -
+ * so the round books the leaf's remaining simulations as visits along its path and parks no leaf: no planes, no
+ * evaluator row (with row compaction the forward after that round is empty), nothing for xq_engine_end_search to
+ * consume.  Terminal leaves back up by the rules as always.  With the carry-over, a game that plays that very leaf has
+ * no expansion to carry: it counts in xq_engine_roots_not_ready and its next root is evaluated in round 0.  Games, visit
+ * counts, pi and z are bit-identical with a deterministic, row-independent evaluator; the TREE after a bare search is
+ * not the reference's (value sums, the last leaf's children), which is why the switch exists.  The caller still calls
+ * its evaluator after every round and xq_engine_end_search after the last.  Valid with root noise, two-network rounds,
+ * the playout cap (a slot's last round is its own), with or without carry-over and cache.  Refused together with tree
+ * reuse (a kept subtree keeps value sums and the leaf's expansion) and virtual loss, in either order of calls. */
+int  xq_engine_set_last_round_visits_only(xq_engine *e, int enable);
+
 /* Evaluator row compaction (off until asked for: row = slot, every slot is evaluated, what the reference does with
  * its per-game batches, self_play.py:139-143).  When on, every xq_engine_search_round is followed by a numbering of
  * the slots that hold a pending leaf, in slot order: the evaluator reads the planes of row r at slot row_src[r],
