@@ -211,8 +211,8 @@ class InferenceNet(nn.Module):
     def __init__(self, net, dtype=torch.bfloat16, c_in=16, device="cuda", policy_columns="reachable", fused_tower=True,
                  allow_library_fallback=False, trunk="bf16"):
         super().__init__()
-        if trunk not in ("bf16", "mxfp8"):
-            raise ValueError("trunk must be 'bf16' or 'mxfp8'")
+        if trunk not in ("bf16", "mxfp8", "mxfp8_256"):
+            raise ValueError("trunk must be 'bf16', 'mxfp8' or 'mxfp8_256'")
         # "mxfp8" (opt-in): the 2 * n_blocks tower convolutions of a 128-channel network on the block-scaled fp8 matrix
         # pipe (csrc/xq_tower_mx.hip: e4m3 x e4m3, fp32 accumulation, the residual stream stays bf16); input convolution,
         # heads and everything behind them as with "bf16"
@@ -221,6 +221,13 @@ class InferenceNet(nn.Module):
             raise ValueError("InferenceNet: trunk='mxfp8' is the single-launch kernel of csrc/xq_tower_mx.hip: 128 channels, "
                              "bfloat16, c_in=16, cuda and fused_tower=True (got channels=%d, dtype=%s, c_in=%d, device=%s, "
                              "fused_tower=%s)" % (net.conv1.out_channels, dtype, c_in, device, fused_tower))
+        # "mxfp8_256" (opt-in): the same for a 256-channel network (csrc/xq_tower256_mx.hip); a value of its own, "mxfp8"
+        # keeps meaning the 128-channel kernel
+        if trunk == "mxfp8_256" and not (net.conv1.out_channels == 256 and dtype == torch.bfloat16 and c_in == 16
+                                         and str(device).startswith("cuda") and fused_tower):
+            raise ValueError("InferenceNet: trunk='mxfp8_256' is the single-launch kernel of csrc/xq_tower256_mx.hip: 256 "
+                             "channels, bfloat16, c_in=16, cuda and fused_tower=True (got channels=%d, dtype=%s, c_in=%d, "
+                             "device=%s, fused_tower=%s)" % (net.conv1.out_channels, dtype, c_in, device, fused_tower))
         self.trunk = trunk
         self.dtype = dtype
         self.fused_tower = fused_tower                 # one launch for the whole trunk (csrc/xq_tower.hip)
@@ -270,15 +277,16 @@ class InferenceNet(nn.Module):
             self.hip_wt = (torch.stack(self.hip_w[1:]).contiguous() if self.n_blocks else
                            torch.zeros((0, 9, self.channels, self.channels), dtype=dtype, device=device))
             self.hip_bt = torch.stack(self.hip_b).contiguous()
-        if trunk == "mxfp8":
+        if trunk in ("mxfp8", "mxfp8_256"):
             # the folded float64 tower weights as [layer][tap][cout][cin], quantised along cin in blocks of 32
-            wt64 = (torch.stack([w.permute(2, 3, 0, 1).reshape(9, 128, 128) for w, _ in convs[1:]]) if self.n_blocks else
-                    torch.zeros((0, 9, 128, 128), dtype=torch.float64))
+            ch = self.channels
+            wt64 = (torch.stack([w.permute(2, 3, 0, 1).reshape(9, ch, ch) for w, _ in convs[1:]]) if self.n_blocks else
+                    torch.zeros((0, 9, ch, ch), dtype=torch.float64))
             wq, ws = mx_quantize(wt64.cpu())
             self.hip_wq, self.hip_ws = wq.to(device).contiguous(), ws.to(device).contiguous()
             # nothing reads the bf16 tower weights on this path: neither uploaded nor part of the rank digest
             self.hip_w = self.hip_w[:1]
-            self.hip_wt = torch.zeros((0, 9, 128, 128), dtype=dtype, device=device)
+            self.hip_wt = torch.zeros((0, 9, ch, ch), dtype=dtype, device=device)
         # heads: the two 1x1 convolutions share one GEMM (32 + 8 output channels)
         pw, pb = _fold_bn(net.policy_conv, net.policy_bn)
         vw, vb = _fold_bn(net.value_conv, net.value_bn)
@@ -340,7 +348,7 @@ class InferenceNet(nn.Module):
             return [p.data for p in self.parameters()]
         return [self.hip_w[0], self.hip_wt, self.hip_bt, self.hip_hw, self.hip_hb, self.pfw.data, self.hip_pfb,
                 self.hip_v1w, self.hip_v1b, self.hip_v2w, self.hip_v2b] + (
-                    [self.hip_wq, self.hip_ws] if self.trunk == "mxfp8" else [])
+                    [self.hip_wq, self.hip_ws] if self.trunk in ("mxfp8", "mxfp8_256") else [])
 
     def _tower_hip(self, x):
         """Residual tower on the hand-written fused conv kernel (csrc/xq_conv.hip): one launch per
@@ -382,7 +390,8 @@ class InferenceNet(nn.Module):
     def trunk_hip(self, x, row_src=None, n_rows=None):
         """planes -> (policy-head activations [G, 2880], value-head activations [G, 720]) in one
         launch of the trunk kernel of the network's width (xq_tower_nhwc_bf16: 128 channels, xq_tower256_nhwc_bf16:
-        256): activations stay in LDS across all layers."""
+        256; trunk="mxfp8" / "mxfp8_256": xq_tower_mxfp8_nhwc / xq_tower256_mxfp8_nhwc): activations stay in LDS across
+        all layers."""
         from . import _lib
         g = x.shape[0]
         xin = x.permute(0, 2, 3, 1)
@@ -393,11 +402,12 @@ class InferenceNet(nn.Module):
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         L = _lib.lib()
-        if self.trunk == "mxfp8":
-            _lib.check(L.xq_tower_mxfp8_nhwc(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
-                                             self.hip_w[0].data_ptr(), self.hip_wq.data_ptr(), self.hip_ws.data_ptr(),
-                                             self.hip_bt.data_ptr(), self.hip_hw.data_ptr(), self.hip_hb.data_ptr(),
-                                             hp.data_ptr(), hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
+        if self.trunk in ("mxfp8", "mxfp8_256"):
+            tower = L.xq_tower256_mxfp8_nhwc if self.trunk == "mxfp8_256" else L.xq_tower_mxfp8_nhwc
+            _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
+                             self.hip_w[0].data_ptr(), self.hip_wq.data_ptr(), self.hip_ws.data_ptr(),
+                             self.hip_bt.data_ptr(), self.hip_hw.data_ptr(), self.hip_hb.data_ptr(),
+                             hp.data_ptr(), hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
         else:
             tower = L.xq_tower256_nhwc_bf16 if self.channels == 256 else L.xq_tower_nhwc_bf16
             _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),

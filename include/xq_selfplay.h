@@ -509,6 +509,19 @@ int  xq_tower_mxfp8_nhwc(void *hip_stream, const void *planes_dev, const void *w
                          void *policy_out_dev, void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev,
                          const void *n_rows_dev);
 
+/* The 256-channel counterpart of xq_tower_mxfp8_nhwc (csrc/xq_tower256_mx.hip), one launch: the arguments and outputs of
+ * xq_tower256_nhwc_bf16 with wt replaced by wq_dev, the OCP e4m3 bytes [2*n_blocks][9][256][256] ([layer][tap][cout][cin]),
+ * and wscale_dev, the E8M0 scale bytes [2*n_blocks][9][256][8] (one per 32 consecutive cin; weight = e4m3 * 2^(byte - 127)).
+ * The arithmetic is xq_tower_mxfp8_nhwc's: input convolution and heads in bf16, tower convolutions e4m3 by e4m3 with fp32
+ * accumulation and fp32 bias, every layer output rounded to bf16 once (the skip added in fp32 before that), the next
+ * operand quantised per pixel and block of 32 consecutive channels by the same rule.  One fixed accumulation order per
+ * output element (bias [+ skip], taps 0..8, input-channel halves 0..1): results do not depend on the launch, the row or
+ * n_boards.  Argument checks, return codes and row_src_dev / n_rows_dev as xq_tower_nhwc_bf16. */
+int  xq_tower256_mxfp8_nhwc(void *hip_stream, const void *planes_dev, const void *w1_dev, const void *wq_dev,
+                            const void *wscale_dev, const void *bias_dev, const void *wh_dev, const void *bh_dev,
+                            void *policy_out_dev, void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev,
+                            const void *n_rows_dev);
+
 /* The policy head's fully-connected layer (neural_network.py:39,64: nn.Linear(32*10*9, 8100) applied to the
  * flattened policy-conv activations): logits[m][n] = bias[n] + sum_k act[m][k] * w[n][k].
  * act [n_rows][k] bf16 (the (h, w, c)-ordered output of xq_tower_nhwc_bf16 / xq_heads_nhwc_bf16), w [n_cols][k]

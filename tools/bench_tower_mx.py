@@ -11,7 +11,10 @@ moves the outputs, against the default bf16 trunk (xq_tower_nhwc_bf16: k_tower1w
   shift     the positions of 1,024 self-play plies (6 blocks, random-init): largest and mean absolute difference of the
             legal-move priors and of the value between the two trunks.  NOT a claim about playing strength.
 
-usage: bench_tower_mx.py [--out-kernel profiles/tower_mx_bench.json] [--out profiles/tower_mx_selfplay.json]"""
+--channels 256 measures the 256-channel pair instead: k_tower256_mx (csrc/xq_tower256_mx.hip, trunk="mxfp8_256") against
+k_tower256 (xq_tower256_nhwc_bf16), the same three parts -> profiles/tower256_mx_bench.json, profiles/tower256_mx_selfplay.json.
+
+usage: bench_tower_mx.py [--channels {128,256}] [--out-kernel profiles/tower_mx_bench.json] [--out profiles/tower_mx_selfplay.json]"""
 import argparse
 import json
 import os
@@ -22,13 +25,18 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ROUNDS, LAUNCHES = 3, 20
+# per width: (trunk value, MX kernel, MX entry point, bf16 kernel, bf16 entry point)
+WIDTHS = {128: ("mxfp8", "k_tower_mx", "xq_tower_mxfp8_nhwc", "k_tower1wa", "xq_tower_nhwc_bf16"),
+          256: ("mxfp8_256", "k_tower256_mx", "xq_tower256_mxfp8_nhwc", "k_tower256", "xq_tower256_nhwc_bf16")}
 
 
 def part_kernel(args):
     import torch
     from chinesechessai_amd import _lib
     from chinesechessai_amd.neural_network import ChessNet, InferenceNet
-    L, G = _lib.lib(), args.games
+    L, G, C = _lib.lib(), args.games, args.channels
+    trunk, mx_name, mx_entry, bf_name, bf_entry = WIDTHS[C]
+    mx_fn, bf_fn = getattr(L, mx_entry), getattr(L, bf_entry)
     st = torch.cuda.current_stream().cuda_stream
     torch.manual_seed(0)
     planes = torch.zeros(G, 10, 9, 16, device="cuda", dtype=torch.bfloat16)
@@ -37,7 +45,7 @@ def part_kernel(args):
     V = torch.empty(G, 720, device="cuda", dtype=torch.bfloat16)
 
     def flop(blocks):                                           # algorithmic count, padding MFMAs not included
-        return 2.0 * G * 90 * (16 * 9 * 128 + 2 * blocks * 128 * 9 * 128 + 128 * 40)
+        return 2.0 * G * 90 * (16 * 9 * C + 2 * blocks * C * 9 * C + C * 40)
 
     def timeit(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -51,17 +59,16 @@ def part_kernel(args):
         return e0.elapsed_time(e1) / LAUNCHES
 
     result = {"boards": G, "launches_per_timing": LAUNCHES, "timings_per_side": ROUNDS, "timer": "HIP events around the launches",
-              "flop": "algorithmic: 2*90*(16*9*128 + 2*blocks*128*9*128 + 128*40) per board", "cases": []}
+              "flop": "algorithmic: 2*90*(16*9*%d + 2*blocks*%d*9*%d + %d*40) per board" % (C, C, C, C), "cases": []}
     for blocks in (6, 20):
         torch.manual_seed(blocks)
-        net = ChessNet(num_channels=128, num_blocks=blocks).eval().cuda()
-        ib, im = InferenceNet(net), InferenceNet(net, trunk="mxfp8")
+        net = ChessNet(num_channels=C, num_blocks=blocks).eval().cuda()
+        ib, im = InferenceNet(net), InferenceNet(net, trunk=trunk)
         head = (ib.hip_hw.data_ptr(), ib.hip_hb.data_ptr(), P.data_ptr(), V.data_ptr(), G, blocks, None, None)
-        sides = (("k_tower_mx", lambda: _lib.check(L.xq_tower_mxfp8_nhwc(st, planes.data_ptr(), im.hip_w[0].data_ptr(),
-                                                                         im.hip_wq.data_ptr(), im.hip_ws.data_ptr(),
-                                                                         im.hip_bt.data_ptr(), *head))),
-                 ("k_tower1wa", lambda: _lib.check(L.xq_tower_nhwc_bf16(st, planes.data_ptr(), ib.hip_w[0].data_ptr(),
-                                                                        ib.hip_wt.data_ptr(), ib.hip_bt.data_ptr(), *head))))
+        sides = ((mx_name, lambda: _lib.check(mx_fn(st, planes.data_ptr(), im.hip_w[0].data_ptr(), im.hip_wq.data_ptr(),
+                                                    im.hip_ws.data_ptr(), im.hip_bt.data_ptr(), *head))),
+                 (bf_name, lambda: _lib.check(bf_fn(st, planes.data_ptr(), ib.hip_w[0].data_ptr(), ib.hip_wt.data_ptr(),
+                                                    ib.hip_bt.data_ptr(), *head))))
         ms = {name: [] for name, _ in sides}
         for _ in range(ROUNDS):                                  # alternating
             for name, fn in sides:
@@ -71,7 +78,7 @@ def part_kernel(args):
             t = ms[name]
             case["sides"][name] = {"ms_per_launch": [round(v, 4) for v in t],
                                    "tflops_algorithmic_best": round(flop(blocks) / min(t) / 1e9, 1)}
-        case["k_tower1wa_fastest_over_k_tower_mx_slowest"] = round(min(ms["k_tower1wa"]) / max(ms["k_tower_mx"]), 3)
+        case["%s_fastest_over_%s_slowest" % (bf_name, mx_name)] = round(min(ms[bf_name]) / max(ms[mx_name]), 3)
         result["cases"].append(case)
         del ib, im, net
         torch.cuda.empty_cache()
@@ -86,7 +93,7 @@ def part_selfplay(args):
     from chinesechessai_amd.neural_network import ChessNet
     G, T = args.games, args.total
     torch.manual_seed(0)
-    net = ChessNet(num_blocks=6).eval().cuda()
+    net = ChessNet(num_channels=args.channels, num_blocks=6).eval().cuda()
     ev = TorchNetEvaluator(net, eval_cache="on", trunk=args.trunk)    # (no adaptive suspension: both legs run the same machinery)
     eng = SelfPlayEngine(G, sims=50, planes_format=ev.planes_format)
     records = torch.zeros(T * _lib.MAX_PLIES * xd.RECORD_BYTES, dtype=torch.uint8, device="cuda")
@@ -111,7 +118,7 @@ def part_shift(args):
     from chinesechessai_amd.engine import SelfPlayEngine, TorchNetEvaluator
     from chinesechessai_amd.neural_network import ChessNet, InferenceNet
     torch.manual_seed(0)
-    net = ChessNet(num_blocks=6).eval().cuda()
+    net = ChessNet(num_channels=args.channels, num_blocks=6).eval().cuda()
     ev = TorchNetEvaluator(net)
     eng = SelfPlayEngine(64, sims=16, planes_format=ev.planes_format, max_moves=16)     # 64 games x 16 plies
     b = eng.play(ev, np.arange(64, dtype=np.uint32))
@@ -122,7 +129,7 @@ def part_shift(args):
     planes[..., :15] = torch.from_numpy(enc).permute(0, 2, 3, 1).to(device="cuda", dtype=torch.bfloat16)
     x = planes.permute(0, 3, 1, 2)
     outs = []
-    for trunk in ("bf16", "mxfp8"):
+    for trunk in ("bf16", WIDTHS[args.channels][0]):
         inet = InferenceNet(net, trunk=trunk)
         logits, values = inet(x)
         outs.append((logits.float().cpu().numpy().astype(np.float64), values.float().cpu().numpy().astype(np.float64), inet.column_map))
@@ -143,7 +150,8 @@ def part_shift(args):
 
 
 def child(args, part, *extra):
-    cmd = [sys.executable, os.path.abspath(__file__), "--part", part, "--games", str(args.games), "--total", str(args.total)] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--part", part, "--games", str(args.games), "--total", str(args.total),
+           "--channels", str(args.channels)] + list(extra)
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=args.part_timeout)
     if pr.returncode != 0:                                   # (a part that failed ends the measurement: nothing more is started)
         sys.exit("part %s %s failed with status %d" % (part, " ".join(extra), pr.returncode))
@@ -156,30 +164,36 @@ def main():
     ap.add_argument("--total", type=int, default=32768, help="games per self-play session")
     ap.add_argument("--repeats", type=int, default=2, help="rounds of alternating self-play processes")
     ap.add_argument("--part-timeout", type=int, default=400, help="seconds one child process may take")
-    ap.add_argument("--out-kernel", default=os.path.join(ROOT, "profiles", "tower_mx_bench.json"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tower_mx_selfplay.json"))
+    ap.add_argument("--channels", type=int, choices=(128, 256), default=128, help="network width: which pair of kernels")
+    ap.add_argument("--out-kernel", default=None, help="default: profiles/tower_mx_bench.json (256: tower256_mx_bench.json)")
+    ap.add_argument("--out", default=None, help="default: profiles/tower_mx_selfplay.json (256: tower256_mx_selfplay.json)")
     ap.add_argument("--part", default="", help="(internal) run this one part in this process")
     ap.add_argument("--trunk", default="bf16", help="(internal) the self-play leg")
     args = ap.parse_args()
     if args.part:
         {"kernel": part_kernel, "selfplay": part_selfplay, "shift": part_shift}[args.part](args)
         return
+    trunk, mx_name, _, bf_name, _ = WIDTHS[args.channels]
+    stem = "tower_mx" if args.channels == 128 else "tower256_mx"
+    args.out_kernel = args.out_kernel or os.path.join(ROOT, "profiles", stem + "_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", stem + "_selfplay.json")
     kernel = child(args, "kernel")
     with open(args.out_kernel, "w") as f:
         json.dump(kernel, f, indent=1)
         f.write("\n")
     for c in kernel["cases"]:
-        print("kernel blocks=%d: %s  fastest k_tower1wa / slowest k_tower_mx = %.3f" % (
-            c["blocks"], {k: v["ms_per_launch"] for k, v in c["sides"].items()}, c["k_tower1wa_fastest_over_k_tower_mx_slowest"]), flush=True)
-    runs = {"bf16": [], "mxfp8": []}
+        print("kernel blocks=%d: %s  fastest %s / slowest %s = %.3f" % (
+            c["blocks"], {k: v["ms_per_launch"] for k, v in c["sides"].items()}, bf_name, mx_name,
+            c["%s_fastest_over_%s_slowest" % (bf_name, mx_name)]), flush=True)
+    runs = {"bf16": [], trunk: []}
     for rnd in range(args.repeats):
         for trunk in runs:
             runs[trunk].append(child(args, "selfplay", "--trunk", trunk))
             print("self-play round %d %s: %.1f games/s" % (rnd, trunk, runs[trunk][-1]["games_per_s"]), flush=True)
     gps = {t: [r["games_per_s"] for r in runs[t]] for t in runs}
     out = {"selfplay": {"slots": args.games, "games": args.total, "sims": 50, "blocks": 6, "runs": runs, "games_per_s": gps,
-                        "mxfp8_slowest_over_bf16_fastest": min(gps["mxfp8"]) / max(gps["bf16"]),
-                        "mxfp8_best_over_bf16_best": max(gps["mxfp8"]) / max(gps["bf16"])},
+                        "mxfp8_slowest_over_bf16_fastest": min(gps[trunk]) / max(gps["bf16"]),
+                        "mxfp8_best_over_bf16_best": max(gps[trunk]) / max(gps["bf16"])},
            "shift": child(args, "shift")}
     print(json.dumps(out), flush=True)
     with open(args.out, "w") as f:
