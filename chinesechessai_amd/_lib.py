@@ -14,13 +14,13 @@ LIB_PATH = os.path.join(CSRC, "libxq_hip.so")
 SOURCES = [os.path.join(CSRC, "xq_engine.hip"), os.path.join(CSRC, "xq_conv.hip"), os.path.join(CSRC, "xq_replay.hip"),
            os.path.join(CSRC, "xq_tower.hip"), os.path.join(CSRC, "xq_policy.hip"), os.path.join(CSRC, "xq_policy_loss.hip"),
            os.path.join(CSRC, "xq_tower256.hip"), os.path.join(CSRC, "xq_tower_mx.hip"), os.path.join(CSRC, "xq_tower256_mx.hip"),
-           os.path.join(CSRC, "xq_tower64.hip")]
-# per-source flags: the 256-channel, the 64-channel and the MXFP8 trunk are compiled without packed fp32 arithmetic (they have no use for it),
+           os.path.join(CSRC, "xq_tower64.hip"), os.path.join(CSRC, "xq_tower192.hip")]
+# per-source flags: the 256-channel, the 192-channel, the 64-channel and the MXFP8 trunk are compiled without packed fp32 arithmetic (they have no use for it),
 # and so is the engine since it gained the last-round builds of the search round (same float32 steps, one lane at a time:
 # 126 / 127 spilled SGPRs in the flagship kernel against 127 / 129 with the packed forms)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"xq_tower256.hip": _NO_PK_F32, "xq_tower_mx.hip": _NO_PK_F32, "xq_tower256_mx.hip": _NO_PK_F32,
-                "xq_tower64.hip": _NO_PK_F32, "xq_engine.hip": _NO_PK_F32}
+                "xq_tower64.hip": _NO_PK_F32, "xq_tower192.hip": _NO_PK_F32, "xq_engine.hip": _NO_PK_F32}
 HEADERS = [os.path.join(CSRC, "xq_device.hpp"), os.path.join(CSRC, "xq_attack.hpp"), os.path.join(CSRC, "xq_mfma.hpp"), os.path.join(CSRC, "xq_tower_args.hpp"), os.path.join(CSRC, "xq_tower_probes.hpp"),
            os.path.join(CSRC, "xq_tower1wa.hpp"), os.path.join(CSRC, "xq_tower1wa_body.inc"), os.path.join(CSRC, "xq_policy_fc1w_body.inc"),
            os.path.join(_HERE, "..", "include", "xq_selfplay.h"), os.path.join(_HERE, "..", "include", "xq_debug.h")]
@@ -208,6 +208,7 @@ _SIGNATURES = {
     "xq_tower_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_tower256_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_tower64_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "xq_tower192_nhwc_bf16": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_tower_mxfp8_nhwc": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_tower256_mxfp8_nhwc": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "xq_policy_fc_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),

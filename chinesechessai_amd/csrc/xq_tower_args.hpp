@@ -1,5 +1,5 @@
 // xq_tower_args.hpp — what the single-launch trunk kernels of every width (xq_tower.hip: 128 channels,
-// xq_tower256.hip: 256 channels, xq_tower64.hip: 64 channels) share on the host side: the kernel argument block and the per-device opt-in to
+// xq_tower256.hip: 256 channels, xq_tower192.hip: 192 channels, xq_tower64.hip: 64 channels) share on the host side: the kernel argument block and the per-device opt-in to
 // more than 64 KB of dynamic LDS.
 #pragma once
 #include "../../include/xq_selfplay.h"
@@ -9,7 +9,7 @@
 
 namespace xqm {
 
-struct TowerArgs {             // C = 64, 128 or 256 channels
+struct TowerArgs {             // C = 64, 128, 192 or 256 channels
     const uint16_t *planes;    // [G][90][16]
     const uint16_t *w1;        // [9][C][16]
     const uint16_t *wt;        // [2*nblocks][9][C][C]

@@ -201,8 +201,8 @@ class InferenceNet(nn.Module):
             keeps the reference's 8,100 columns in order (padded to 8,256 on the hand-written path).  Callers that
             index logits by move must go through column_map (the engine does: xq_engine_set_logit_columns).
 
-    The hand-written kernels cover dtype=bfloat16, c_in=16 (channels-last), 64, 128 or 256 channels on a CUDA device (64
-    and 256: the single-launch trunk only, fused_tower=False raises); any other configuration raises ValueError unless
+    The hand-written kernels cover dtype=bfloat16, c_in=16 (channels-last), 64, 128, 192 or 256 channels on a CUDA device (64,
+    192 and 256: the single-launch trunk only, fused_tower=False raises); any other configuration raises ValueError unless
     allow_library_fallback=True asks for PyTorch's library kernels.
     row_src / n_rows (device pointers from SelfPlayEngine.row_map(), hand-written fused path only): evaluator row
     compaction - row r reads the planes of x[row_src[r]], writes outputs to row r, rows >= *n_rows are skipped.
@@ -253,12 +253,12 @@ class InferenceNet(nn.Module):
         # hand-written fused conv path: weights as [tap][cout][cin] bf16, bias fp32
         self.channels = net.conv1.out_channels
         self.use_hip_conv = (dtype == torch.bfloat16 and c_in == 16 and str(device).startswith("cuda")
-                             and self.channels in (64, 128, 256))
+                             and self.channels in (64, 128, 192, 256))
         if not self.use_hip_conv and not allow_library_fallback:
-            # the hand-written kernels cover bf16, channels-last 16-plane input, 64, 128 or 256 channels; anything else
+            # the hand-written kernels cover bf16, channels-last 16-plane input, 64, 128, 192 or 256 channels; anything else
             # would run on library kernels (MIOpen / hipBLASLt): only on request, never silently
             raise ValueError("InferenceNet: no hand-written HIP path for dtype=%s, c_in=%d, channels=%d, device=%s (the "
-                             "kernels cover bfloat16, c_in=16, 64, 128 or 256 channels, cuda); "
+                             "kernels cover bfloat16, c_in=16, 64, 128, 192 or 256 channels, cuda); "
                              "pass allow_library_fallback=True to run this configuration on PyTorch's library kernels "
                              "(parity / debugging runs only)" % (dtype, c_in, self.channels, device))
         if self.use_hip_conv and self.channels != 128 and not fused_tower:
@@ -391,7 +391,7 @@ class InferenceNet(nn.Module):
     def trunk_hip(self, x, row_src=None, n_rows=None):
         """planes -> (policy-head activations [G, 2880], value-head activations [G, 720]) in one
         launch of the trunk kernel of the network's width (xq_tower64_nhwc_bf16: 64 channels, xq_tower_nhwc_bf16: 128,
-        xq_tower256_nhwc_bf16: 256; trunk="mxfp8" / "mxfp8_256": xq_tower_mxfp8_nhwc / xq_tower256_mxfp8_nhwc): activations stay in LDS across
+        xq_tower192_nhwc_bf16: 192, xq_tower256_nhwc_bf16: 256; trunk="mxfp8" / "mxfp8_256": xq_tower_mxfp8_nhwc / xq_tower256_mxfp8_nhwc): activations stay in LDS across
         all layers."""
         from . import _lib
         g = x.shape[0]
@@ -410,7 +410,8 @@ class InferenceNet(nn.Module):
                              self.hip_bt.data_ptr(), self.hip_hw.data_ptr(), self.hip_hb.data_ptr(),
                              hp.data_ptr(), hv.data_ptr(), g, self.n_blocks, row_src, n_rows))
         else:
-            tower = {64: L.xq_tower64_nhwc_bf16, 128: L.xq_tower_nhwc_bf16, 256: L.xq_tower256_nhwc_bf16}[self.channels]
+            tower = {64: L.xq_tower64_nhwc_bf16, 128: L.xq_tower_nhwc_bf16, 192: L.xq_tower192_nhwc_bf16,
+                     256: L.xq_tower256_nhwc_bf16}[self.channels]
             _lib.check(tower(torch.cuda.current_stream().cuda_stream, xin.data_ptr(),
                              self.hip_w[0].data_ptr(), self.hip_wt.data_ptr(), self.hip_bt.data_ptr(),
                              self.hip_hw.data_ptr(), self.hip_hb.data_ptr(), hp.data_ptr(),

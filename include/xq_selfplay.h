@@ -504,6 +504,17 @@ int  xq_tower64_nhwc_bf16(void *hip_stream, const void *planes_dev, const void *
                           const void *bias_dev, const void *wh_dev, const void *bh_dev, void *policy_out_dev,
                           void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev, const void *n_rows_dev);
 
+/* The same trunk for a 192-channel network (neural_network.py:47-71,172-187, BN folded), one launch of its own kernel
+ * (csrc/xq_tower192.hip): conv3x3(16->192)+ReLU, n_blocks residual blocks, both 1x1 heads + ReLU; activations never leave
+ * LDS between layers.  planes [n][10][9][16] bf16, w1 [9][192][16] bf16, wt [2*n_blocks][9][192][192] bf16, bias float32
+ * [1 + 2*n_blocks][192] (conv1 first), wh [64][192] bf16 (rows 0..31 policy, 32..39 value, rest zero), bh float32[64];
+ * outputs, arithmetic (bf16 storage between layers, fp32 accumulation in one fixed order per element, the skip added in
+ * fp32 before a block's single rounding), argument checks, return codes and row_src_dev / n_rows_dev as
+ * xq_tower_nhwc_bf16. */
+int  xq_tower192_nhwc_bf16(void *hip_stream, const void *planes_dev, const void *w1_dev, const void *wt_dev,
+                           const void *bias_dev, const void *wh_dev, const void *bh_dev, void *policy_out_dev,
+                           void *value_out_dev, int n_boards, int n_blocks, const void *row_src_dev, const void *n_rows_dev);
+
 /* The 128-channel trunk with its 2 * n_blocks tower convolutions in MXFP8 (csrc/xq_tower_mx.hip), one launch.  The
  * arguments of xq_tower_nhwc_bf16 with wt replaced by wq_dev, the OCP e4m3 bytes [2*n_blocks][9][128][128]
  * ([layer][tap][cout][cin]), and wscale_dev, the E8M0 scale bytes [2*n_blocks][9][128][4] (one per 32 consecutive
