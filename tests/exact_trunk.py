@@ -9,6 +9,7 @@ of every layer; the tests assert headroom < 2^24 before they compare anything.
 
 Plain torch on the CPU, nothing here touches a GPU."""
 import collections
+import math
 
 import torch
 import torch.nn.functional as F
@@ -163,3 +164,234 @@ def first_difference(got, ref):
     b, p, c = d[0].tolist()
     return "%d of %d outputs differ; first at board %d pixel %d channel %d: kernel 0x%04x, chain 0x%04x" % (
         len(d), ref.numel(), b, p, c, got[b, p, c].item() & 0xFFFF, ref[b, p, c].item() & 0xFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The MXFP8 trunk kernels (csrc/xq_tower_mx.hip, csrc/xq_tower256_mx.hip) on integer-valued networks.
+#
+# The argument carries over ("Bit-exact integer networks"): an integer quantised to e4m3 under a power-of-two
+# block scale is an integer again (where the e4m3 step is below 1 the integer is kept, where it is 1 or more the result is
+# a multiple of it), and a weight of the form integer x 2^j with at most 4 significant bits survives mx_quantize exactly.
+# So every e4m3 x e4m3 product is an integer, every fp32 partial sum is exact in any order while the sum of |terms| stays
+# below 2^24, and the bf16 rounding and the quantisation that follow are functions of an exact number: the in-kernel
+# quantiser is pinned in every bit at every layer.
+
+MxNet = collections.namedtuple("MxNet", "w1 wq wscale bias wh bh")
+MxChain = collections.namedtuple("MxChain", "bits headroom plus_one at_boundary changed ties subnormal flushed "
+                                            "act_scales w_scales boundary_lossy")
+# (blocks, k, jmax) of both MXFP8 kernels: a tower weight block of 32 input channels is multiplied by 2^j, j in 0..jmax
+# ((6, 5, 1) was (6, 6, 1) until k_tower256_mx differed from the chain there in one output of 10,800, see MX_EXACT;
+# its 256-channel net has a seed of its own, see MX_NET_SEEDS)
+MX_DEPTHS = ((0, 0, 0), (1, DENSE, 3), (2, 24, 3), (6, 6, 0), (6, 5, 1), (20, 2, 0))
+MX_SUBNORMAL_CASES = ((6, 5, 1), (20, 2, 0))        # the cases that must reach 1,000 e4m3 subnormals
+# The cases in which a "+1" that fires at mantissa exactly 1.75 must change a head bit, at both widths.  That rule equals
+# the right one unless a block at 1.75 holds an element that one more scale step pushes below 2^-6 (MxChain.boundary_lossy:
+# e4m3 is a floating-point format, everywhere else halving an element costs it nothing), which needs a block maximum of
+# 2^14 or more beside odd elements of a few units: (6, 5, 1) has 13 to 40 such elements, no other case has one.  Whether
+# one of them reaches a head output depends on the net.  At 128 channels NET_SEED does it on the CPU planes and on the
+# GPU module's (2 and 3 outputs).  At 256 channels it does not (18 and 16 elements, no output), so that case has a net
+# seed of its own: the first of 0..199 with which the mutant shows on both sets of planes (1 output each; with planes of
+# one set alone seeds 1, 11, 15 or 4, 8, 14 would do).
+MX_BOUNDARY_CASES = ((6, 5, 1),)
+MX_NET_SEEDS = {(256, 6, 5, 1): 28}                 # (channels, blocks, k, jmax): every other case has NET_SEED
+# The headroom under which every MXFP8 case matched its chain on an MI355X.  v_mfma_scale_f32_16x16x128_f8f6f4 does not
+# always deliver the exact sum of its 128 products where fp32 could hold it: at (6, 6, 1), 256 channels, headroom 2^23.27,
+# one last-layer sum of -13,312 (an earlier tap) + 393,216 - 8 (both in one instruction and one K block, the 8 from an
+# e4m3 subnormal) came out at least 8 too large, the product 2^15.6 times smaller than its neighbour lost; the same
+# network at 128 channels matched at 2^23.75, so the headroom is a stand-in for the spread of the products inside one
+# instruction.  The largest headroom below the failure that matched is 2^22.87 ((6, 5, 1), 128 channels).  DESIGN.md §7.
+MX_EXACT = 2 ** 23
+MX_SEED = 9                                          # of the draw of j
+
+# Mutants of mx_chain; each changes one thing.
+MX_TRUNCATE = "e4m3 conversion by truncation"
+MX_TIES_AWAY = "e4m3 ties away from zero"
+MX_NO_PLUS_ONE = "no +1 rule, elements saturate at 448"
+MX_PLUS_ONE_AT_BOUNDARY = "+1 rule fires at mantissa 1.75"
+MX_FP32_SUM = "quantiser reads the fp32 sum"
+MX_FLUSH = "e4m3 subnormals flushed to zero"
+MX_WEIGHT_SCALE = "weight scale byte of K-block q ^ 1 in the last tower layer"
+MX_ACT_SCALE = "activation scale byte of channel block q ^ 1 in the last tower layer"
+MX_MUTANTS = (MX_TRUNCATE, MX_TIES_AWAY, MX_NO_PLUS_ONE, MX_PLUS_ONE_AT_BOUNDARY, MX_FP32_SUM, MX_FLUSH, MX_WEIGHT_SCALE,
+              MX_ACT_SCALE)
+MX_LAST_LAYER_MUTANTS = (MX_WEIGHT_SCALE, MX_ACT_SCALE)
+
+
+def mx_cases(channels):
+    """(blocks, k, jmax, G) of one MXFP8 kernel: the dense block at all three board counts (NB = 4 boards per workgroup in
+    xq_tower_mx.hip, 2 in xq_tower256_mx.hip: one board into a second and into a third workgroup), every other depth at the
+    middle one."""
+    lo, mid, hi = BOARDS[channels]
+    out = []
+    for blocks, k, jmax in MX_DEPTHS:
+        out += [(blocks, k, jmax, g) for g in ((lo, mid, hi) if k == DENSE else (mid,))]
+    return out
+
+
+def mx_net_seed(channels, blocks, k, jmax):
+    """The net seed of an MXFP8 case: NET_SEED but for the cases of MX_NET_SEEDS."""
+    return MX_NET_SEEDS.get((channels, blocks, k, jmax), NET_SEED)
+
+
+def integer_net_mx(channels, blocks, k, jmax, seed):
+    """integer_net's tensors with every tower weight block of 32 consecutive input channels, per (layer, tap, cout,
+    K-block), multiplied by 2^j, j drawn from 0..jmax (seed MX_SEED), through mx_quantize: w1, wq e4m3 bytes
+    [2 * blocks][9][C][C], wscale E8M0 bytes [2 * blocks][9][C][C / 32], bias, wh, bh - what the MXFP8 C entries read.
+    The bytes dequantise to the integer weights exactly (+-2^j has one significant bit)."""
+    from chinesechessai_amd.neural_network import mx_dequantize, mx_quantize
+    C = channels
+    t = integer_net(C, blocks, k, seed)
+    g = torch.Generator().manual_seed(MX_SEED)
+    j = torch.randint(0, jmax + 1, (2 * blocks, 9, C, C // 32), generator=g)
+    wt = torch.ldexp(t.wt.double().view(2 * blocks, 9, C, C // 32, 32), j.unsqueeze(-1)).view(2 * blocks, 9, C, C)
+    wq, ws = mx_quantize(wt)
+    assert wq.shape == (2 * blocks, 9, C, C) and ws.shape == (2 * blocks, 9, C, C // 32)
+    assert torch.equal(mx_dequantize(wq, ws), wt) and torch.equal(wt, wt.round())
+    return MxNet(t.w1, wq.contiguous(), ws.contiguous(), t.bias, t.wh, t.bh)
+
+
+def _swap_neighbours(x):
+    """Along the last axis: element q takes the place of element q ^ 1."""
+    return x.reshape(x.shape[:-1] + (x.shape[-1] // 2, 2)).flip(-1).reshape(x.shape)
+
+
+def mx_activation(x, mutant=None, swap_scales=False, stats=None):
+    """mx_dequantize(*mx_quantize(x)) of non-negative activations [..., C] (float64), restated so that one step of it can
+    be wrong: per block of 32 consecutive channels m = the maximum, e = floor(log2 m) - 8, + 1 when m * 2^-e > 448 (the
+    mantissa of m above 1.75), scale byte e + 127 (127 for an all-zero block), elements x * 2^-e rounded to nearest-even
+    e4m3 (step 2^(floor(log2 y) - 3), 2^-9 below 2^-6), times 2^e.  With no mutant the result is asserted equal to
+    mx_quantize's.  swap_scales: block q is scaled back by the byte of block q ^ 1.  stats: a dict whose event counts, taken
+    by the right rule over the non-zero blocks whatever the mutant, are added to."""
+    from chinesechessai_amd.neural_network import mx_dequantize, mx_quantize
+    assert x.dtype == torch.float64 and bool((x >= 0).all())
+    xb = x.reshape(x.shape[:-1] + (x.shape[-1] // 32, 32))
+    m = xb.amax(-1)
+    nz = m > 0
+    e = torch.where(nz, torch.frexp(m)[1].to(torch.int64) - 9, torch.zeros_like(m, dtype=torch.int64))
+    top = torch.ldexp(m, -e)                                         # in [256, 512): 256 x the mantissa of m
+    plus = {MX_NO_PLUS_ONE: torch.zeros_like(nz), MX_PLUS_ONE_AT_BOUNDARY: top >= 448}.get(mutant, top > 448)
+    byte = torch.where(nz, e + plus.to(torch.int64) + 127, torch.full_like(e, 127))
+    assert 0 <= int(byte.min()) and int(byte.max()) <= 254
+    y = torch.ldexp(xb, (127 - byte).unsqueeze(-1))
+    step = torch.ldexp(torch.ones_like(y), (torch.frexp(y)[1].to(torch.int64) - 1).clamp(min=-6) - 3)
+    r = y / step
+    if mutant == MX_TRUNCATE:
+        v = torch.floor(r) * step
+    elif mutant == MX_TIES_AWAY:
+        v = torch.floor(r + 0.5) * step
+    else:
+        v = torch.round(r) * step                                    # (torch.round: halves to even)
+    sub = (y > 0) & (y < 2.0 ** -6)
+    if mutant == MX_FLUSH:
+        v = torch.where(sub, torch.zeros_like(v), v)
+    if mutant == MX_NO_PLUS_ONE:
+        v = v.clamp(max=448.0)
+    assert float(v.max()) <= 448.0
+    out = torch.ldexp(v, ((_swap_neighbours(byte) if swap_scales else byte) - 127).unsqueeze(-1)).reshape(x.shape)
+    if mutant is None and not swap_scales:
+        assert torch.equal(out, mx_dequantize(*mx_quantize(x)))
+    if stats is not None:
+        stats["plus_one"] += int((nz & (top > 448)).sum())
+        stats["at_boundary"] += int((nz & (top == 448)).sum())
+        stats["changed"] += int((out != x).sum())
+        stats["ties"] += int(((y > 0) & (r - torch.floor(r) == 0.5)).sum())
+        stats["subnormal"] += int(sub.sum())
+        stats["flushed"] += int((sub & (v == 0)).sum())
+        # e4m3 is a floating-point format: one scale step more costs an element a bit only where it then lies below 2^-6
+        half_step = torch.ldexp(torch.ones_like(y), (torch.frexp(y)[1].to(torch.int64) - 2).clamp(min=-6) - 3)
+        stats["boundary_lossy"] += int(((nz & (top == 448)).unsqueeze(-1) & (torch.round(y / 2 / half_step) * half_step * 2 != v)).sum())
+        stats["act_scales"].update(byte[nz].unique().tolist())
+    return out
+
+
+def mx_chain(t, planes, blocks, mutant=None, dtype=torch.float64, last_layer_input=None):
+    """float64_chain for the MXFP8 kernels: t is integer_net_mx's MxNet; in front of every tower convolution the
+    bf16-rounded activation goes through mx_dequantize(*mx_quantize(.)) (mx_activation), the weights are mx_dequantize of
+    the bytes.  Per layer: conv1 as in bf16; per block y = rne(relu(convq(a) + bias)), a = rne(relu(convq(y) + bias + a)),
+    the skip a taken as the unquantised bf16 stream; the heads read that stream.  Returns MxChain: the head bit patterns
+    and the headroom (on the quantised operands) as float64_chain, and the quantiser's events over all non-zero activation
+    blocks that a tower convolution reads: blocks where the "+1" rule fired, blocks whose maximum has mantissa exactly
+    1.75 (where it must not fire), elements whose quantisation changed the value, elements that were exact ties on the
+    e4m3 grid, elements in the e4m3 subnormal range (below 2^-6 after scaling) and how many of those became zero, the
+    number of distinct activation scale bytes and of distinct weight scale bytes, and (boundary_lossy) the elements of
+    blocks at mantissa 1.75 that a scale byte one higher would quantise to another value - the only place where
+    MX_PLUS_ONE_AT_BOUNDARY can show.  mutant: one of MX_MUTANTS; of a mutant's run only the bits mean anything (headroom
+    and counts are not taken: 0).  last_layer_input: a dict that the right chain fills with what the last tower layer reads
+    and that a mutant of that layer alone (MX_LAST_LAYER_MUTANTS), given the same t and planes, starts from."""
+    from chinesechessai_amd.neural_network import mx_dequantize
+    assert mutant is None or mutant in MX_MUTANTS
+    C = t.w1.shape[1]
+    stats = {"headroom": 0.0, "plus_one": 0, "at_boundary": 0, "changed": 0, "ties": 0, "subnormal": 0, "flushed": 0,
+             "act_scales": set(), "boundary_lossy": 0}
+    last = 2 * blocks - 1
+
+    def kernel(w):                                      # [9][cout][cin] -> [cout][cin][3][3]
+        return w.to(dtype).reshape(3, 3, w.shape[1], -1).permute(2, 3, 0, 1)
+
+    def room(v):
+        stats["headroom"] = max(stats["headroom"], v.max().item())
+
+    def conv(x, w, b, skip=None):
+        if mutant is None:                              # a mutant's headroom and counts are nobody's business: not taken
+            room(F.conv2d(x.abs(), kernel(w).abs(), b.to(dtype).abs(), padding=1) + (0 if skip is None else skip.abs()))
+        return F.conv2d(x, kernel(w), b.to(dtype), padding=1)
+
+    def convq(s, a, i, skip=None):                      # s: the exact fp32 sum after the ReLU, a = rne(s)
+        x = (s if mutant == MX_FP32_SUM else a).double().permute(0, 2, 3, 1)
+        xq = mx_activation(x, mutant, swap_scales=mutant == MX_ACT_SCALE and i == last,
+                           stats=stats if mutant is None else None)
+        scale = _swap_neighbours(t.wscale[i]) if mutant == MX_WEIGHT_SCALE and i == last else t.wscale[i]
+        w = mx_dequantize(t.wq[i], scale)
+        # integers stay integers (a block scaled back by its neighbour's byte may not)
+        assert mutant == MX_ACT_SCALE or (torch.equal(xq, xq.round()) and torch.equal(w, w.round()))
+        return conv(xq.permute(0, 3, 1, 2).to(dtype), w, t.bias[1 + i], skip)
+    if blocks and mutant in MX_LAST_LAYER_MUTANTS and last_layer_input:
+        s1, y, a = last_layer_input["s1 y a"]           # of the right chain on the same t and planes: equal up to here
+    else:
+        s = torch.relu(conv(planes.to(dtype).permute(0, 3, 1, 2), t.w1, t.bias[0]))
+        a = rne(s)
+        for i in range(blocks):
+            s1 = torch.relu(convq(s, a, 2 * i))
+            y = rne(s1)
+            if i == blocks - 1:
+                break
+            s = torch.relu(convq(s1, y, 2 * i + 1, skip=a) + a)
+            a = rne(s)
+        if blocks and mutant is None and last_layer_input is not None:
+            last_layer_input["s1 y a"] = (s1, y, a)
+    if blocks:
+        s = torch.relu(convq(s1, y, last, skip=a) + a)
+        a = rne(s)
+    x = a.permute(0, 2, 3, 1).reshape(-1, 90, C)
+    if mutant is None:
+        room(x.abs() @ t.wh[:40].to(dtype).abs().t() + t.bh[:40].to(dtype).abs())
+    h = rne(torch.relu(x @ t.wh[:40].to(dtype).t() + t.bh[:40].to(dtype))) + 0.0        # + 0.0: a zero is +0
+    return MxChain(h.bfloat16().contiguous().view(torch.int16), stats["headroom"], stats["plus_one"], stats["at_boundary"],
+                   stats["changed"], stats["ties"], stats["subnormal"], stats["flushed"], len(stats["act_scales"]),
+                   len(t.wscale.unique()), stats["boundary_lossy"])
+
+
+def mx_assert_reached(ch, channels, blocks, k, jmax, G):
+    """What a run of a case must reach before anything is compared with it: the headroom that makes every fp32 sum exact
+    and, from one block up, enough quantiser events of every kind for a wrong rule to show.  The counts are those of the
+    case at its middle board count (and above); the dense block's one-board run has G / middle of the activation blocks
+    and is asked for that share (at 128 channels it has 720 blocks in all, 360 of them conv1's, the only ones whose
+    small maxima sit at mantissa 1.75 often: 100 such blocks cannot be reached there).  In numbers, at one board: 20 "+1"
+    blocks, 20 blocks at 1.75, 200 ties and 200 changed values at 128 channels (1 board of 5), 34, 34, 334 and 334 at 256
+    (1 of 3); reached there: 101, 50, 666, 5,385 and 200, 89, 1,114, 10,069."""
+    share = min(1.0, G / BOARDS[channels][1])
+    assert ch.headroom < MX_EXACT < EXACT, "headroom 2^%.2f" % math.log2(ch.headroom)
+    if blocks == 0:
+        # the stem and the heads alone: outputs are non-negative integers no larger than the headroom, which is below
+        # 100, so they cannot take 100 values; what is left to ask is that they vary (as for the bf16 kernels)
+        assert ch.headroom < 100 and len(ch.bits.unique()) > 10
+    else:
+        assert len(ch.bits.unique()) >= 100
+        assert ch.plus_one >= 100 * share and ch.at_boundary >= 100 * share, ch[1:]
+        assert ch.ties >= 1000 * share and ch.changed >= 1000 * share and ch.act_scales >= 4, ch[1:]
+    if jmax == 3:
+        assert ch.w_scales >= 4, ch[1:]
+    if (blocks, k, jmax) in MX_SUBNORMAL_CASES:
+        assert ch.subnormal >= 1000, ch[1:]
+    if (blocks, k, jmax) in MX_BOUNDARY_CASES:
+        assert ch.boundary_lossy > 0, ch[1:]

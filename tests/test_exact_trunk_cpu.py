@@ -93,3 +93,137 @@ def test_float32_chain_equals_float64_chain(channels, blocks, k, G):
     c32 = X.float64_chain(t, planes, blocks, dtype=torch.float32)
     assert X.first_difference(c32.bits, ch.bits) is None, X.first_difference(c32.bits, ch.bits)
     assert (c32.headroom, c32.changed, c32.ties) == (ch.headroom, ch.changed, ch.ties)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The MXFP8 cases of tests/test_gpu_trunk_exact_mx.py
+
+MX_CASES = [(c,) + case for c in (128, 256) for case in X.mx_cases(c)]
+MX_TOWER_CASES = [case for case in MX_CASES if case[1] > 0]
+# what test_trunk*_mx_against_float64_chain's bound (old_bound) accepts on these networks, as measured on the CPU: these
+# two mutants in every case, every other mutant in none (their largest error is 1.03 to 6,463 times the bound)
+MX_OLD_BOUND_ACCEPTS = {X.MX_PLUS_ONE_AT_BOUNDARY, X.MX_FLUSH}
+
+
+@functools.lru_cache(maxsize=None)
+def _mx_case(channels, blocks, k, jmax, G):
+    t = X.integer_net_mx(channels, blocks, k, jmax, X.mx_net_seed(channels, blocks, k, jmax))
+    planes = X.cpu_planes(G, X.PLANES_SEED)
+    last = {}
+    return t, planes, X.mx_chain(t, planes, blocks, last_layer_input=last), last
+
+
+def test_integer_net_mx_is_what_it_says():
+    from chinesechessai_amd.neural_network import mx_dequantize
+    t, base = X.integer_net_mx(128, 2, 24, 3, 3), X.integer_net(128, 2, 24, 3)
+    assert t.wq.shape == (4, 9, 128, 128) and t.wscale.shape == (4, 9, 128, 4) and t.wq.dtype == t.wscale.dtype == torch.uint8
+    for name in ("w1", "bias", "wh", "bh"):
+        assert torch.equal(getattr(t, name), getattr(base, name))
+    w = mx_dequantize(t.wq, t.wscale).view(4, 9, 128, 4, 32)
+    ratio = w / base.wt.double().view(4, 9, 128, 4, 32)             # nan where the integer weight is zero
+    assert set(ratio[~ratio.isnan()].unique().tolist()) == {1.0, 2.0, 4.0, 8.0}
+    live = ~ratio.isnan()
+    assert (torch.where(live, ratio, ratio.nan_to_num(0).amax(-1, keepdim=True)) == ratio.nan_to_num(0).amax(-1, keepdim=True)).all()
+    assert torch.equal(w == 0, base.wt.double().view(4, 9, 128, 4, 32) == 0)
+    # the scale byte of a block whose largest weight is 2^j is j - 8 + 127; an all-zero block has 127
+    assert set(t.wscale.unique().tolist()) <= {119, 120, 121, 122, 127} and len(t.wscale.unique()) >= 4
+    empty = X.integer_net_mx(256, 0, 0, 0, 0)
+    assert empty.wq.shape == (0, 9, 256, 256) and empty.wscale.shape == (0, 9, 256, 8)
+
+
+def test_mx_activation_on_known_values():
+    """One block each; the scale puts the maximum into [256, 512), e4m3 then steps by 32 from 256 and by 2^-9 below 2^-6."""
+    def q(values, **kw):
+        x = torch.zeros(32, dtype=torch.float64)
+        x[:len(values)] = torch.tensor(values, dtype=torch.float64)
+        return X.mx_activation(x, **kw)[:len(values)].tolist()
+    # maximum 28 = 1.75 * 16 is the boundary: scale 2^-4, 28 -> 448; 17 -> 272 is a tie between 256 and 288, 19 -> 304
+    # one between 288 and 320; with the +1 fired nothing here changes (e4m3 is floating point), so the values are equal
+    assert q([28, 17, 19, 21, 3]) == [28, 16, 20, 20, 3]
+    assert q([28, 17, 19, 21, 3], mutant=X.MX_PLUS_ONE_AT_BOUNDARY) == [28, 16, 20, 20, 3]
+    assert q([28, 17, 19, 21, 3], mutant=X.MX_TRUNCATE) == [28, 16, 18, 20, 3]
+    assert q([28, 17, 19, 21, 3], mutant=X.MX_TIES_AWAY) == [28, 18, 20, 22, 3]
+    # maximum 29 > 1.75 * 16: the +1 fires, 29 -> 232 is a tie between 224 and 240; without it 29 -> 464, a tie between
+    # 448 and 480, and 31 -> 496 -> 480 saturates to 448 = 28
+    assert q([29, 31 - 2]) == [28, 28] and q([31, 30]) == [32, 30]
+    assert q([31, 30], mutant=X.MX_NO_PLUS_ONE) == [28, 28]
+    # maximum 2^15 -> 256 (scale 2^7): 1 -> 2^-7 is subnormal (step 2^-9 = a quarter unit: kept), 3 -> 3 * 2^-7 is normal;
+    # the flush mutant loses the 1
+    assert q([32768, 1, 3]) == [32768, 1, 3] and q([32768, 1, 3], mutant=X.MX_FLUSH) == [32768, 0, 3]
+    # maximum 2^18 -> 256 (scale 2^10): the subnormal step is 2 units: 1 is a tie and goes to 0, 3 to 4, 5 to 4, 7 to 8
+    assert q([262144, 1, 3, 5, 7, 9]) == [262144, 0, 4, 4, 8, 8]
+    # maximum 1.75 * 2^17 at the boundary (scale 2^9, subnormal step 1); one scale step more and the step is 2 units
+    assert q([229376, 1, 3, 5]) == [229376, 1, 3, 5]
+    assert q([229376, 1, 3, 5], mutant=X.MX_PLUS_ONE_AT_BOUNDARY) == [229376, 0, 4, 4]
+    stats = {k: 0 for k in ("plus_one", "at_boundary", "changed", "ties", "subnormal", "flushed", "boundary_lossy")}
+    stats["act_scales"] = set()
+    X.mx_activation(torch.tensor([229376.0, 1, 3, 5] + [0.0] * 60, dtype=torch.float64), stats=stats)
+    assert stats == {"plus_one": 0, "at_boundary": 1, "changed": 0, "ties": 0, "subnormal": 3, "flushed": 0,
+                     "boundary_lossy": 3, "act_scales": {127 + 9}}
+    # the neighbour's scale byte: block 0 (scale 2^-4) comes back under block 1's (2^-3) and the other way round
+    two = torch.tensor([28.0] + [0.0] * 31 + [56.0] + [0.0] * 31, dtype=torch.float64)
+    assert X.mx_activation(two, swap_scales=True)[[0, 32]].tolist() == [56, 28]
+
+
+@pytest.mark.parametrize("channels,blocks,k,jmax,G", MX_CASES)
+def test_mx_headroom_and_quantiser_events(channels, blocks, k, jmax, G):
+    """Every case of the MXFP8 GPU module on CPU planes of the same density: headroom below 2^23 (X.MX_EXACT: measured,
+    below the 2^24 of the fp32 significand), head outputs that vary, and from one block up the quantiser's events - 100
+    blocks where the +1 fired, 100 at mantissa exactly 1.75, 1,000 e4m3 ties, 1,000 changed values, 4 activation scale
+    bytes; 4 weight scale bytes with jmax = 3; 1,000 subnormals in (6, 5, 1) and (20, 2, 0); in (6, 5, 1) an element that
+    a +1 at 1.75 would change (X.mx_assert_reached; the dense block's one-board run is asked for its share of the blocks,
+    the runs from the middle count up for the whole thresholds, here once more)."""
+    t, planes, ch, last = _mx_case(channels, blocks, k, jmax, G)
+    print("C=%d blocks=%d k=%s jmax=%d G=%d: headroom 2^%.2f, +1 in %d blocks, %d at 1.75, %d values changed, %d ties, %d "
+          "subnormal (%d to zero), %d / %d activation / weight scale bytes, %d lossy at the boundary, %d distinct outputs" % (
+              channels, blocks, "dense" if k == X.DENSE else k, jmax, G, math.log2(ch.headroom), ch.plus_one, ch.at_boundary,
+              ch.changed, ch.ties, ch.subnormal, ch.flushed, ch.act_scales, ch.w_scales, ch.boundary_lossy,
+              len(ch.bits.unique())))
+    assert ch.bits.shape == (G, 90, 40)
+    X.mx_assert_reached(ch, channels, blocks, k, jmax, G)
+    if blocks == 0:
+        assert ch[2:] == (0,) * 9                                    # no tower: nothing is quantised
+        assert torch.equal(ch.bits, X.float64_chain(X.integer_net(channels, 0, 0, X.NET_SEED), planes, 0).bits)
+    elif G >= X.BOARDS[channels][1]:
+        assert min(ch.plus_one, ch.at_boundary) >= 100 and min(ch.ties, ch.changed) >= 1000 and ch.act_scales >= 4
+
+
+@pytest.mark.parametrize("channels,blocks,k,jmax,G", MX_CASES)
+def test_mx_float32_chain_equals_float64_chain(channels, blocks, k, jmax, G):
+    t, planes, ch, last = _mx_case(channels, blocks, k, jmax, G)
+    c32 = X.mx_chain(t, planes, blocks, dtype=torch.float32)
+    assert X.first_difference(c32.bits, ch.bits) is None, X.first_difference(c32.bits, ch.bits)
+    assert c32[1:] == ch[1:]
+
+
+@pytest.mark.parametrize("channels,blocks,k,jmax,G", MX_TOWER_CASES)
+def test_mx_mutants_change_a_bit(channels, blocks, k, jmax, G):
+    """Eight wrong quantisers or scale routings.  Truncation, ties away, the missing +1, the fp32 sum and both misrouted
+    scale bytes change a head bit in every case with a tower; flushed subnormals in the cases that assert subnormals.
+    The +1 at exactly 1.75 changes a head bit in (6, 5, 1) at both widths (X.MX_BOUNDARY_CASES, where the 256-channel net
+    has a seed of its own for it) and equals the right rule wherever boundary_lossy is 0 (asserted: no test can tell it
+    apart there).  With each: its max-norm error against the bound of test_trunk*_mx_against_float64_chain, asserted as
+    measured (MX_OLD_BOUND_ACCEPTS): a statement about that test, not a tolerance of this one.  The two mutants of the
+    last tower layer start from the right chain's input to that layer."""
+    t, planes, ch, last = _mx_case(channels, blocks, k, jmax, G)
+    ref = ch.bits.view(torch.bfloat16).double()
+    bound = X.old_bound(ch.bits, blocks)
+    for name in X.MX_MUTANTS:
+        m = X.mx_chain(t, planes, blocks, mutant=name, last_layer_input=last).bits
+        if name in X.MX_LAST_LAYER_MUTANTS and G == 1:              # the short cut, once per width against the whole chain
+            assert last and torch.equal(m, X.mx_chain(t, planes, blocks, mutant=name).bits)
+        differ = int((m != ch.bits).sum())
+        err =(m.view(torch.bfloat16).double() - ref).abs().max().item()
+        print("C=%d blocks=%d k=%d jmax=%d G=%d mutant %-70s %6d outputs differ, max-norm error / old bound = %.4f" % (
+            channels, blocks, k, jmax, G, name + ":", differ, err / bound))
+        if name == X.MX_PLUS_ONE_AT_BOUNDARY:
+            if (blocks, k, jmax) in X.MX_BOUNDARY_CASES:
+                assert differ > 0, name
+            assert ch.boundary_lossy > 0 or differ == 0
+        elif name == X.MX_FLUSH:
+            if (blocks, k, jmax) in X.MX_SUBNORMAL_CASES:
+                assert differ > 0, name
+            assert ch.subnormal > 0 or differ == 0
+        else:
+            assert differ > 0, name
+        assert (err <= bound) == (name in MX_OLD_BOUND_ACCEPTS), name
